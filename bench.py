@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the NLP-callback hot path: cycles/sec of (f, grad f, g, J, H) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A *step* is one NLP-callback cycle (systembase.py:602-835 of the reference): objective, gradient,
@@ -10,12 +10,16 @@ planar_quadrotor re-meshed on LGR 2000 intervals x 6 points = 12 000 nodes (conf
 lambda ~ N(0,1), sigma = 1, all seeded.  N > 1: 2000*N intervals of the same model sharded by mesh interval over the N GPUs
 (weak scaling), figures in 12k-node-equivalent cycles/s.
 
-What is printed: rank 0 prints ONE short JSON line LAST (strict JSON, < 4 KB, fixed keys: tools/benchlib/line.py) and
-writes everything else it measured -- timing statistics, per-callback tables, side kernels, the other BASELINE workloads --
-to ``bench_detail.json`` beside this file (and to gpurun_out/ when that directory exists).
+What is printed: rank 0 prints ONE short JSON line LAST (strict JSON, < 4 KB, fixed keys: tools/benchlib/line.py).
 * ``value`` / ``ms_per_step`` / ``device_resident``: the cycle with x, lambda and all outputs resident in HBM, ONE pk_cycle
-  launch per cycle; R back-to-back batches of EXACTLY ``steps`` launches, HIP events on the launch stream, barrier +
-  synchronize around the region, median batch / steps, max over ranks.  ``roofline`` is computed from this region.
+  launch per cycle; after ``warmup`` untimed cycles, EXACTLY ``steps`` timed cycles back to back, in batches of up to 200
+  with a HIP event on the launch stream after each, barrier + synchronize around the region; ``ms_per_step`` = median over
+  the batches of batch time / cycles in it, max over ranks.  ``roofline`` is computed from this region.
+* ``--dump-outputs DIR``: f, grad f, g, J, H as the last timed cycle left them, ``DIR/<name>.npy`` in float64 (a fixed,
+  seeded sample of each array if all of them together exceed 64 MB).
+
+A plain run measures the headline alone.  ``--full`` adds everything else, and writes it to ``bench_detail.json`` beside
+this file: per-dispatch kernel times, side kernels, the other BASELINE workloads, and
 * ``end_to_end``: the host-landed (solver-visible) cycle -- the five callbacks of ``System`` on a new x, NumPy arrays in,
   caller-owned NumPy arrays out, reference triplet layout; PCIe-inclusive, therefore never ``value``.
 * ``cpu_baseline``: the oracle (CPU restatement of the reference) on the same workload and inputs, one host thread, a
@@ -55,20 +59,33 @@ def __getattr__(name):
 
 
 def write_detail(detail):
-    """bench_detail.json beside bench.py (+ a copy under gpurun_out/ when present, so that it comes back from a GPU box)."""
+    """bench_detail.json beside bench.py (``--full`` runs)."""
     text = json.dumps(L.sanitize(detail), allow_nan=False, indent=1)
-    paths = [os.path.join(ROOT, "bench_detail.json")]
-    if os.path.isdir(os.path.join(ROOT, "gpurun_out")):
-        paths.append(os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
-    written = None
-    for p in paths:
-        try:
-            with open(p, "w") as fh:
-                fh.write(text)
-            written = written or os.path.relpath(p, ROOT)
-        except OSError:
-            pass
-    return written
+    path = os.path.join(ROOT, "bench_detail.json")
+    try:
+        with open(path, "w") as fh:
+            fh.write(text)
+    except OSError:
+        return None
+    return os.path.relpath(path, ROOT)
+
+
+DUMP_LIMIT = 64 * 2**20       # bytes of all arrays written by --dump-outputs
+
+
+def dump_outputs(outdir, outputs):
+    """f, grad f, g, J, H of the last timed cycle as ``outdir/<name>.npy`` (float64); above DUMP_LIMIT in all, the same fixed,
+    seeded sample of each array (sorted positions) is written instead."""
+    import numpy as np
+
+    arrays = {k: np.atleast_1d(np.asarray(a, dtype=np.float64)).ravel() for k, a in zip(("f", "grad", "g", "J", "H"), outputs)}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        if total > DUMP_LIMIT:
+            keep = max(1, a.size * (DUMP_LIMIT - 8 * len(arrays)) // total)      # (f, a single number, is always kept)
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(outdir, k + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -87,14 +104,20 @@ def spawn_ranks(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)        # cycles per batch; the region is R batches, >= 50 ms in total
-    ap.add_argument("--warmup", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=20000, help="timed cycles")
+    ap.add_argument("--warmup", type=int, default=2000, help="untimed cycles before them (at least 500 on one GPU)")
     ap.add_argument("--workload", default="planar_quadrotor")
     ap.add_argument("--intervals", type=int, default=2000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the supplementary workloads")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (CPU baseline and parity, "
+                                                        "kernel and side figures, end-to-end cycle, other workloads) and write "
+                                                        "bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the supplementary workloads")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the host-landed cycle")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -105,6 +128,8 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU "
                          f"(python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus} ...)")
+    if args.dump_outputs and world > 1:
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1 (with N > 1 the outputs stay split over the ranks)")
 
     import torch
 
@@ -125,38 +150,45 @@ def main():
 
             dist = HostStagedCollectives(dist)
     n_gpus = world
+    full = args.full
 
     intervals = args.intervals * n_gpus          # weak scaling: per-GPU share stays args.intervals
+    with_cpu_baseline = full and not args.no_cpu_baseline and n_gpus == 1
     res = measure(args.workload, intervals, args.steps, args.warmup, rank, world, dist,
-                  with_e2e=not args.no_end_to_end, keep_outputs=not args.no_cpu_baseline)
+                  with_e2e=full and not args.no_end_to_end, e2e_steps=min(args.steps, 200),
+                  keep_outputs=with_cpu_baseline or bool(args.dump_outputs), full=full)
     t = torch.tensor([res["ms_per_step"], res["wall_ms_per_step"]], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     ms, wall_ms = float(t[0].item()), float(t[1].item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["outputs"])
 
     # N > 1: BASELINE.json's sharded configs at their full size, STRONG-scaled over the N GPUs (every rank takes part)
-    # (they feed the line's fixed key multi_gpu.strong, so they run unless --no-extra asks for the headline alone)
-    strong = strong_scaled_workloads(args, rank, world, dist) if (world > 1 and not args.no_extra) else {}
+    # (they feed the line's fixed key multi_gpu.strong)
+    strong = strong_scaled_workloads(args, rank, world, dist) if (world > 1 and full and not args.no_extra) else {}
 
     if rank == 0:
         e2e = res.get("end_to_end") if world == 1 else res.get("end_to_end_host_sharded")
-        detail = L.detail_record(args, res, e2e, n_gpus, intervals, ms, wall_ms, ROOT)
         cb, parity = None, None
-        if not args.no_cpu_baseline and n_gpus == 1:      # (required by the contract: a failure here is a failure of the run)
-            cb, parity = cpu_baseline(args.workload, intervals, gpu_outputs=res.get("outputs"))
-            detail["cpu_baseline"], detail["parity"] = cb, parity
-        if n_gpus == 1 and not args.no_extra:
-            try:
-                detail["compile_s_cold"] = cold_compile_seconds(args.workload, intervals)
-            except Exception as exc:  # noqa: BLE001
-                detail["compile_s_cold"] = repr(exc)
-            detail["other_workloads"] = other_workloads(args)
-        elif n_gpus > 1 and not args.no_extra:
-            detail["other_workloads"] = strong
+        if full:
+            detail = L.detail_record(args, res, e2e, n_gpus, intervals, ms, wall_ms, ROOT)
+            if with_cpu_baseline:      # (a failure here is a failure of the run)
+                cb, parity = cpu_baseline(args.workload, intervals, gpu_outputs=res.get("outputs"))
+                detail["cpu_baseline"], detail["parity"] = cb, parity
+            if n_gpus == 1 and not args.no_extra:
+                try:
+                    detail["compile_s_cold"] = cold_compile_seconds(args.workload, intervals)
+                except Exception as exc:  # noqa: BLE001
+                    detail["compile_s_cold"] = repr(exc)
+                detail["other_workloads"] = other_workloads(args)
+            elif n_gpus > 1 and not args.no_extra:
+                detail["other_workloads"] = strong
         short_parity = None if parity is None else {k: parity[k] for k in ("max_rel_err", "tol", "ok")}
         line = L.short_line(args, res, e2e, n_gpus, intervals, ms, ROOT, cpu_baseline=cb, parity=short_parity, strong=strong)
-        detail["line"] = line
-        line["detail_file"] = write_detail(detail)
+        if full:
+            detail["line"] = line
+            line["detail_file"] = write_detail(detail)
         sys.stdout.flush()
         print(L.dumps_line(line), flush=True)
     if world > 1:

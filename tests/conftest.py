@@ -26,6 +26,70 @@ def pytest_sessionstart(session):
                 pass
 
 
+@pytest.hookimpl(trylast=True)
+def pytest_collection_modifyitems(config, items):
+    """A GPU session on a machine with a device: compile the selected tests' models in a second process with several
+    workers while the tests run (tools/compile_only.py) -- a fresh checkout has none of them in pockit_amd/_cache.
+    POCKIT_AMD_PREFETCH=0 turns this off."""
+    gpu = [it.nodeid for it in items if it.get_closest_marker("gpu")]
+    if (not gpu or os.environ.get("POCKIT_AMD_COMPILE_ONLY") or os.environ.get("PYTEST_XDIST_WORKER")
+            or os.environ.get("POCKIT_AMD_PREFETCH", "1") == "0" or not os.path.exists("/dev/kfd")):
+        return
+    import subprocess
+    import tempfile
+
+    from pockit_amd import hipbuild
+    from tools import compile_only
+
+    compile_only.remove_stale_markers()
+    hipbuild.compile_model = compile_only.guarded_compile(hipbuild.compile_model, wait=True)
+    fd, ids = tempfile.mkstemp(prefix="pockit_amd_gpu_tests_", suffix=".txt")
+    with os.fdopen(fd, "w") as fh:
+        fh.write("\n".join(gpu) + "\n")
+    cpus = min(16, int(os.environ.get("MAX_JOBS") or 0) or len(os.sched_getaffinity(0)))
+    jobs = []
+    try:
+        import xdist  # noqa: F401
+
+        if cpus > 3:
+            jobs = ["-n", str(cpus - 2)]        # (two CPUs stay with the session that drives the GPU)
+    except ImportError:
+        pass
+    env = dict(os.environ, POCKIT_AMD_COMPILE_ONLY="1", POCKIT_AMD_COMPILE_LOG=os.devnull, POCKIT_AMD_USED_LOG=os.devnull,
+               PYTHONDONTWRITEBYTECODE="1", PYTHONPATH=os.pathsep.join(p for p in (ROOT, os.environ.get("PYTHONPATH")) if p))
+    proc = subprocess.Popen([sys.executable, "-m", "pytest", "@" + ids, "-q", "-p", "no:cacheprovider", "-p", "tools.compile_only",
+                             "--tb=no", "--no-header", "--disable-warnings", "-rN"] + jobs,
+                            cwd=str(config.rootpath), env=env, stdin=subprocess.DEVNULL, stdout=subprocess.DEVNULL,
+                            stderr=subprocess.DEVNULL, start_new_session=True)
+    config._pockit_prefetch = (proc, ids)
+
+
+def pytest_unconfigure(config):
+    prefetch = getattr(config, "_pockit_prefetch", None)
+    if prefetch is None:
+        return
+    import signal
+    import subprocess
+
+    proc, ids = prefetch
+    if proc.poll() is None:
+        try:
+            os.killpg(proc.pid, signal.SIGTERM)
+            proc.wait(timeout=20)
+        except subprocess.TimeoutExpired:
+            os.killpg(proc.pid, signal.SIGKILL)
+            proc.wait()
+        except OSError:
+            pass
+    try:
+        os.remove(ids)
+    except OSError:
+        pass
+    from tools import compile_only
+
+    compile_only.remove_stale_markers()
+
+
 def pytest_terminal_summary(terminalreporter):
     """How much of the session went into hipcc: the GPU suite is sized for a warm code-object cache (pockit_amd/_cache, filled
     without a GPU by tools/warm_cache.sh and shipped with the tree).  Objects compiled here mean the cache was cold for them

@@ -74,3 +74,37 @@ def test_the_detail_record_is_strict_json_too_and_keeps_the_long_tables():
     back = json.loads(text)
     assert back["end_to_end"]["what"] == "x" * 3000 and back["mesh_error_estimation"]["pk_err_us"] is None
     assert back["roofline"]["kernel"] == "pk_cycle" and back["device_resident"]["timing"]["batches"] == 500
+
+
+def test_a_plain_run_line_keeps_the_fixed_keys_without_the_extras():
+    """bench.py without --full: no CPU baseline, parity, per-dispatch or side figures, end-to-end cycle -- the same keys, null."""
+    args = argparse.Namespace(steps=20000, warmup=2000, workload="planar_quadrotor", gpus=1)
+    res, _, _, _ = canned()
+    res.update(dispatch_isolated_us=None, dispatch_in_flight_us=None, dispatch_samples=None, kernel_us={}, side={})
+    back = json.loads(L.dumps_line(L.short_line(args, res, None, 1, 2000, res["ms_per_step"], ROOT)))
+    for key in REQUIRED:
+        assert key in back, key
+    assert back["ms_per_step"] == pytest.approx(res["ms_per_step"]) and back["steps"] == 20000
+    assert back["cpu_baseline"] is None and back["parity"] is None and back["end_to_end"] is None
+    assert back["roofline"]["frac"] is not None
+
+
+def test_dumped_outputs_are_float64_and_a_sample_above_the_limit_is_the_same_every_time(tmp_path, monkeypatch):
+    import numpy as np
+
+    import bench
+
+    outs = (np.float64(1.5), np.arange(10.0), np.arange(5.0) - 2, np.linspace(0, 1, 100), np.arange(50.0) * 3)
+    bench.dump_outputs(str(tmp_path / "whole"), outs)
+    for name, a in zip(("f", "grad", "g", "J", "H"), outs):
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, np.atleast_1d(a))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 400)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outs)
+    total = 0
+    for name in ("f", "grad", "g", "J", "H"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(a, b) and a.size >= 1
+        total += a.nbytes
+    assert 0 < total <= 400

@@ -188,9 +188,10 @@ def detail_record(args, res, e2e, n_gpus, intervals, ms, wall_ms, root):
             "value": n_gpus * 1e3 / ms, "ms_per_step": ms,
             "unit": "cycles/s" if n_gpus == 1 else "12k-node-equivalent cycles/s",
             "what": "x and lambda resident in HBM, all outputs left in HBM: ONE pk_cycle launch per cycle and GPU",
-            "timing": {"region": f"{res['batches']} back-to-back batches of exactly {args.steps} cycles, a HIP event on the launch "
-                                 f"stream after every {res['event_group']} batches, barrier + synchronize around the region; "
-                                 f"ms_per_step = median over the timed units / batches / steps (max over ranks)",
+            "timing": {"region": f"exactly {args.steps} back-to-back cycles in {res['batches']} batches of up to "
+                                 f"{res.get('batch_steps', args.steps)}, a HIP event on the launch stream after every batch, "
+                                 f"barrier + synchronize around the region; ms_per_step = median over the batches of batch time / "
+                                 f"cycles in it (max over ranks)",
                        "batches": res["batches"], "batches_per_timing_event": res["event_group"], "batch_launch": res["batch_launch"],
                        "median_batch_ms": res["median_batch_ms"],
                        "batch_ms_min_p10_p90_max": [res["batch_ms_min"], res["batch_ms_p10"], res["batch_ms_p90"], res["batch_ms_max"]],

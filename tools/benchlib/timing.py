@@ -9,7 +9,7 @@ import time
 
 import numpy as np
 
-from .workloads import (EVENT_SPACING, ISOLATED_SAMPLES, KERNEL_IDS, MIN_REGION_S, MIN_WARMUP, algorithmic_bytes, build_workload,
+from .workloads import (EVENT_SPACING, ISOLATED_SAMPLES, KERNEL_IDS, MIN_WARMUP, algorithmic_bytes, build_workload,
                         side_roofline, solver_inputs)
 
 def pcie_floor(plan, shipped_J):
@@ -523,45 +523,40 @@ class GpuWorkload:
             self.torch.cuda.synchronize()
 
     def timed_region(self, steps, warmup):
-        """Warm-up, then R back-to-back batches of exactly ``steps`` cycles (events between the batches on the launch
-        stream), bracketed by barrier + synchronize.  Returns the batch durations (ms) and the wall clock."""
+        """Warm-up, then EXACTLY ``steps`` back-to-back cycles: batches of ``B = min(steps, EVENT_SPACING)`` cycles with a HIP
+        event on the launch stream after every batch (the last batch holds the remainder), bracketed by barrier +
+        synchronize.  Returns the duration of every batch (ms), the cycles in each, the wall clock of the region and the
+        number of untimed cycles before it."""
         torch, step, stream = self.torch, self.step, self.stream
         n_warm = max(warmup, MIN_WARMUP) if self.world == 1 else max(warmup, 3)
         for _ in range(n_warm):
             step()
         self.sync()
-        # size of the region: estimate the step time on a short untimed stretch
-        t0 = time.perf_counter()
-        probe = max(steps, 1000 if self.world == 1 else 20)     # (long enough for the closing synchronize not to count)
-        for _ in range(probe):
-            step()
-        self.sync()
-        est = (time.perf_counter() - t0) / probe
-        R = int(min(4000, max(5, -(-MIN_REGION_S // (est * steps)))))
-        if self.world > 1:                                   # every rank must run the same number of batches
-            t = torch.tensor([R], dtype=torch.int64, device=self.dev)
-            self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
-            R = int(t.item())
-        # How a batch reaches the stream (one GPU): `steps` kernel launches enqueued by the library, or ONE replay of a
-        # hipGraph of `steps` kernel nodes (pk_set_cycle_graph: 0.4 us of host time per cycle instead of ~4, a kernel
+        B = max(1, min(steps, EVENT_SPACING))
+        sizes = [B] * (steps // B) + ([steps % B] if steps % B else [])
+        probe = 0
+        # How a batch reaches the stream (one GPU): `B` kernel launches enqueued by the library, or ONE replay of a
+        # hipGraph of `B` kernel nodes (pk_set_cycle_graph: 0.4 us of host time per cycle instead of ~4, a kernel
         # ~2 % longer).  On a box whose host needs longer per launch than the kernel runs the first form is paced by the
         # host; both are timed on a short stretch and the faster one carries the region.
-        self.batch_launch = {"form": f"{steps} kernel launches per batch"}
+        self.batch_launch = {"form": f"{B} kernel launches per batch"}
+        use_graph = False
         if self.world == 1 and hasattr(step, "many") and self.dominant == "pk_cycle" and os.environ.get("POCKIT_AMD_BENCH_GRAPH", "auto") != "0":
             ms = {}
             for form in ("launches", "graph"):
                 try:
                     self.ev.set_cycle_graph(form == "graph")
-                    step.many(steps)                               # (captures the graph)
+                    step.many(B)                                   # (captures the graph)
                     self.sync()
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    nb = max(10, 4000 // steps)
+                    nb = max(10, 4000 // B)
                     e0.record(stream)
                     for _ in range(nb):
-                        step.many(steps)
+                        step.many(B)
                     e1.record(stream)
                     self.sync()
-                    ms[form] = e0.elapsed_time(e1) / (nb * steps)
+                    ms[form] = e0.elapsed_time(e1) / (nb * B)
+                    probe += (nb + 1) * B
                 except Exception as exc:  # noqa: BLE001 -- a box whose runtime refuses the capture keeps the plain launches
                     if form == "launches":
                         raise
@@ -572,37 +567,38 @@ class GpuWorkload:
             use_graph = ms["graph"] < float("inf") and (ms["graph"] < ms["launches"] or os.environ.get("POCKIT_AMD_BENCH_GRAPH") == "1")
             self.ev.set_cycle_graph(use_graph)
             if use_graph:
-                step.many(steps)
+                step.many(B)
                 self.sync()
-            self.batch_launch = {"form": (f"one hipGraph of {steps} kernel nodes per batch" if use_graph
-                                          else f"{steps} kernel launches per batch"),
+                probe += B
+            self.batch_launch = {"form": (f"one hipGraph of {B} kernel nodes per batch" if use_graph
+                                          else f"{B} kernel launches per batch"),
                                  "probe_us_per_cycle": {k: (v * 1e3 if v < float("inf") else None) for k, v in ms.items()}}
-        # An event between two launches is not free: it drains the stream (measured: ~3 us of GPU time each, 3 % of a
-        # 20-cycle batch).  Events are therefore recorded after every `group` batches, group * steps >= EVENT_SPACING
-        # cycles; a timed unit is `group` whole batches and its duration / group is what enters the statistics.
-        group = max(1, -(-EVENT_SPACING // steps))
-        R = -(-R // group) * group
-        events = [torch.cuda.Event(enable_timing=True) for _ in range(R // group + 1)]
+            if use_graph and len(sizes) > 1 and sizes[-1] != B:
+                self.batch_launch["remainder"] = f"the last {sizes[-1]} cycles as plain launches"
+        # An event between two launches is not free: it drains the stream (measured: ~3 us of GPU time each), hence one
+        # event per batch of up to EVENT_SPACING cycles.
+        events = [torch.cuda.Event(enable_timing=True) for _ in range(len(sizes) + 1)]
         self.sync()
         t0 = time.perf_counter()
         events[0].record(stream)
-        many = getattr(step, "many", None)      # a batch = ONE call into the library that enqueues `steps` cycles
-        for b in range(R):
+        many = getattr(step, "many", None)      # a batch = ONE call into the library that enqueues the batch's cycles
+        for b, count in enumerate(sizes):
             if many is not None:
-                many(steps)
+                if use_graph and count != B:        # (a graph of another length would be captured inside the region)
+                    self.ev.set_cycle_graph(False)
+                many(count)
             else:
-                for _ in range(steps):
+                for _ in range(count):
                     step()
-            if (b + 1) % group == 0:
-                events[(b + 1) // group].record(stream)
+            events[b + 1].record(stream)
         self.sync()
         wall = time.perf_counter() - t0
-        batch_ms = [events[u].elapsed_time(events[u + 1]) / group for u in range(R // group)]
-        self.event_group = group
-        self.region_batches = R
+        batch_ms = [events[u].elapsed_time(events[u + 1]) for u in range(len(sizes))]
+        self.event_group = 1
+        self.region_batches = len(sizes)
         if self.world == 1 and hasattr(step, "many"):
             self.ev.set_cycle_graph(False)
-        return batch_ms, wall, n_warm + probe
+        return batch_ms, sizes, wall, n_warm + probe
 
     def dispatch_times(self, kernel):
         """Per-dispatch duration of ``kernel`` from HIP events attached to the dispatch itself
@@ -725,21 +721,35 @@ class GpuWorkload:
 
 
 def measure(name, intervals, steps, warmup, rank, world, dist, with_side=True, with_e2e=True, e2e_steps=None, e2e_warmup=None,
-            keep_outputs=False):
-    """Everything the JSON line says about one workload on this rank."""
+            keep_outputs=False, full=True):
+    """Everything the JSON line says about one workload on this rank.  ``full=False``: the timed region alone (set-up,
+    warm-up, exactly ``steps`` timed cycles) -- no per-dispatch timings, side kernels, exchange forms or end-to-end cycle.
+    ``keep_outputs``: ``res["outputs"]`` = (f, grad, g, J, H) as the last timed cycle left them."""
     w = GpuWorkload(name, intervals, rank, world, dist)
-    batch_ms, wall, untimed = w.timed_region(steps, warmup)
+    batch_ms, sizes, wall, untimed = w.timed_region(steps, warmup)
     R = w.region_batches
-    med = statistics.median(batch_ms)
-    q = sorted(batch_ms)
+    per_step = [t / c for t, c in zip(batch_ms, sizes)]
+    B = sizes[0]
+    med = statistics.median(per_step) * B
+    q = sorted(t * B for t in per_step)         # (batch durations scaled to full batches of B cycles)
     Rq = len(q)
     res = dict(name=name, intervals=intervals, nodes=int(sum(pp.layout.L_m for pp in w.plan.phase_plans)),
-               n=w.plan.n, m=w.plan.m, nnz_J=w.plan.nnz_J, nnz_H=w.plan.nnz_H, steps=steps, batches=R,
-               median_batch_ms=med, ms_per_step=med / steps, event_group=w.event_group, batch_launch=w.batch_launch,
+               n=w.plan.n, m=w.plan.m, nnz_J=w.plan.nnz_J, nnz_H=w.plan.nnz_H, steps=steps, batch_steps=B, batches=R,
+               median_batch_ms=med, ms_per_step=med / B, event_group=w.event_group, batch_launch=w.batch_launch,
                batch_ms_p10=q[int(0.1 * (Rq - 1))], batch_ms_p90=q[int(0.9 * (Rq - 1))], batch_ms_min=q[0], batch_ms_max=q[-1],
-               region_wall_s=wall, wall_ms_per_step=wall / (R * steps) * 1e3, untimed_launches=untimed,
+               region_wall_s=wall, wall_ms_per_step=wall / steps * 1e3, untimed_launches=untimed,
                setup_s=w.setup_s, compile_s_in_setup=w.compile_s_in_setup, bytes=w.bytes, dominant=w.dominant,
                exchange=w.exchange, tiles=int(len(w.ev.tables.tiles)), ipw=int(w.ev.tables.intervals_per_wave))
+    if keep_outputs and world == 1:      # what the last timed cycle computed (the caller's arrays of the timed path)
+        w.sync()
+        res["outputs"] = tuple(w.o[k].cpu().numpy().copy() for k in ("f", "grad", "g", "J", "H"))
+    if not full:
+        res.update(no_exchange_ms_per_step=None, exchange_forms_ms_per_step=None, ranks=None, dispatch_isolated_us=None,
+                   dispatch_in_flight_us=None, dispatch_samples=None, kernel_us={}, side={}, end_to_end=None, finite=w.finite())
+        if world > 1:
+            res["multi_gpu"] = multi_gpu_facts(w.torch, dist, rank, world, w)
+        w.close()
+        return res
     # N > 1: the same loop without the exchange (every rank keeps its slices), to separate the kernels from the collectives
     res["no_exchange_ms_per_step"] = None
     if world > 1 and w.fused:
@@ -805,10 +815,6 @@ def measure(name, intervals, steps, warmup, rank, world, dist, with_side=True, w
     except Exception as exc:  # noqa: BLE001
         res["side"] = {"side_kernels_error": repr(exc)}
     res["end_to_end"] = None
-    if keep_outputs and world == 1:      # the GPU path's results on the bench inputs, for the line's parity check against the oracle
-        w.step()
-        w.sync()
-        res["outputs"] = tuple(w.o[k].cpu().numpy().copy() for k in ("f", "grad", "g", "J", "H"))
     w.close()
     if with_e2e and world == 1:
         import pockit_amd.radau as radau

@@ -13,7 +13,7 @@ repo=${GRAFT_REPO_ROOT:-$PWD}
 out=$repo/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-python3 "$repo/bench.py" --steps 20 --warmup 5 > "$out/${tag}_bench_n1.json" 2> "$out/${tag}_bench_n1.err" || exit 1
+python3 "$repo/bench.py" --full --steps 20 --warmup 5 > "$out/${tag}_bench_n1.json" 2> "$out/${tag}_bench_n1.err" || exit 1
 cp "$repo/bench_detail.json" "$out/${tag}_bench_detail.json" 2>/dev/null
 tail -c 600 "$out/${tag}_bench_n1.json"
 BENCH_ARGS="--steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-end-to-end"
