@@ -118,6 +118,11 @@ void pk_destroy(pk_ctx* ctx);
 const char* pk_last_error(pk_ctx* ctx); /* ctx may be NULL: last error of a failed pk_create */
 int pk_device_count(void);
 
+/* Loads the code object and checks the descriptor.  Error 21: a kernel every model launches (pockit_amd/csrc/pk_launch.h;
+ * pk_cyclec with every compact role the descriptor has expressions for) would ask for more than 160 KiB of LDS per workgroup
+ * -- expression counts, the cycle's larger staging area and the compact roles included, so a descriptor no launch could
+ * serve is refused here and not by its first launch (error 22).  Code objects of pockit_amd.evaluator.compile_plan pass
+ * by construction (ModelSource.fits_lds counts the same bytes). */
 int pk_load_model(pk_ctx* ctx, const void* code_object, size_t len, const pk_model_desc* md);
 int pk_set_problem(pk_ctx* ctx, const pk_problem_desc* pd);
 int pk_get_structure(pk_ctx* ctx, int32_t* jac_row, int32_t* jac_col, int32_t* hess_row, int32_t* hess_col);

@@ -325,9 +325,12 @@ class ModelSource:
         self.hash = hashlib.sha256(self.source.encode()).hexdigest()[:24]
 
     def launch_lds_bytes(self):
-        """Dynamic LDS per workgroup of every tile kernel's launch, exactly as csrc/pk_runtime.cpp sizes it (launch_raw adds
-        the table blocks of the workgroup's four waves to what the entry point asks for): {kernel: bytes}.  What
-        evaluator.compile_plan holds against LDS_LIMIT, and pk_load_model checks again."""
+        """Dynamic LDS per workgroup of every tile kernel's launch, the table blocks of the workgroup's four waves included:
+        {kernel: bytes}.  What evaluator.compile_plan holds against LDS_LIMIT.  The library sizes its launches, and
+        pk_load_model checks a descriptor, with csrc/pk_launch.h; tests/test_cabi.py holds the two against each other: equal
+        for a single-GPU code object, and for a sharded one never below the library's figure (the exchange vectors of
+        pk_cycle / pk_cyclec are counted in front of the table block here, under it there).  pk_cyclec: the layout with every
+        compact role the model has."""
         w = 8 * 4
         tab = w * (2 * self.tab_cap + 2 * 64 + self.tab_cap // 2)
         ne = lambda cb: 8 * self.list_off[cb]["total"] if cb in self.list_off else 0  # noqa: E731

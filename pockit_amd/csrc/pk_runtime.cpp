@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <atomic>
 #include <chrono>
 #include <memory>
@@ -39,14 +40,10 @@
 #include "../../include/pockit_hip.h"
 #define PK_MAX_PHASES 128     // (= PK_HOST_MAX_PHASES: the host-side PkArgs holds the most a code object may ask for)
 #include "pk_abi.h"
+#include "pk_launch.h"        // kernel ids and names; grid and LDS bytes of every launch
 
 namespace {
 
-enum { K_INT = 0, K_FIN, K_G, K_GRAD, K_JAC, K_HESS, K_XALL, K_AUX, K_OUTER, K_HESSC, K_ERR, K_CSR, K_CYCLE, K_XCHG, K_RUNS, K_JACC,
-       K_CYCLEC, K_COUNT };
-const char* const kKernelNames[K_COUNT] = {"pk_int", "pk_fin", "pk_g", "pk_grad", "pk_jac", "pk_hess", "pk_xall",
-                                           "pk_aux", "pk_outer", "pk_hessc", "pk_err", "pk_csr", "pk_cycle", "pk_xchg", "pk_runs",
-                                           "pk_jacc", "pk_cyclec"};
 enum { F_WRITE_F = 1, F_SECONDARY = 2, F_FIN_INT = 8, F_FIN_GRAD = 16, F_SPLIT = 32, F_XCHG = 64, F_NO_HESS = 128,
        F_COMPACT_H = 256, F_COMPACT_J = 512 };
 
@@ -335,16 +332,18 @@ size_t args_bytes(const pk_ctx* c) {
   return offsetof(PkArgs, ph) + sizeof(PkPhase) * (size_t)(c->md.max_phases > 0 ? c->md.max_phases : 8);
 }
 
-int launch_raw(pk_ctx* c, int k, void* args, size_t sz, unsigned grid, size_t lds_bytes, hipStream_t st) {
+// pk_launch_shape with the facts of the context's problem (n_flat: entries of pk_csr / chunks of pk_runs; layout: pk_cyclec's)
+PkLaunchShape shape_of(const pk_ctx* c, int k, int64_t n_flat = 0, int layout = 0) {
+  return pk_launch_shape(k, c->md, {c->n_tiles, c->split_xall, c->xc_inline && c->xc_world > 1, layout, c->n_outer, c->n_erriv, n_flat});
+}
+
+int launch_raw(pk_ctx* c, int k, void* args, size_t sz, const PkLaunchShape& shape, hipStream_t st) {
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   EventPair ev{};
+  const unsigned grid = shape.grid;
   if (grid == 0) return 0;
-  // the tile kernels that stage their pattern tables keep one table block per wave in front of the model's staging area
-  if (k == K_G || k == K_JAC || k == K_HESS || k == K_XALL || k == K_CYCLE || k == K_CYCLEC || k == K_JACC || k == K_HESSC)
-    lds_bytes += sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)(2 * c->md.tab_cap + 2 * PK_WAVE + c->md.tab_cap / 2);
-  if ((k == K_CYCLE || k == K_CYCLEC) && c->xc_inline && c->xc_world > 1 && lds_bytes < sizeof(double) * 2 * 512)
-    lds_bytes = sizeof(double) * 2 * 512;      // the finalize workgroup's exchange vectors (2 x PK_XC_CAP doubles)
-  if (lds_bytes > 160 * 1024) return fail(c, 22, "%s needs %zu bytes of LDS per workgroup (> 160 KiB)", kKernelNames[k], lds_bytes);
+  if (shape.lds_bytes > PK_LDS_LIMIT)
+    return fail(c, 22, "%s needs %zu bytes of LDS per workgroup (> 160 KiB)", kKernelNames[k], shape.lds_bytes);
   // every `profile_period`-th launch of a selected kernel is timed (the timed launch path costs ~2-3 us of host
   // and command-processor work, so timing all of them would slow the loop being measured)
   const bool timed = c->profiling && ((c->profile_mask >> k) & 1u) && (c->profile_seen[k]++ % c->profile_period == 0);
@@ -359,16 +358,16 @@ int launch_raw(pk_ctx* c, int k, void* args, size_t sz, unsigned grid, size_t ld
       PK_HIP(c, hipEventCreate(&ev.a));
       PK_HIP(c, hipEventCreate(&ev.b));
     }
-    PK_HIP(c, hipExtModuleLaunchKernel(c->fn[k], grid * PK_BLOCK, 1, 1, PK_BLOCK, 1, 1, lds_bytes, st, nullptr, config,
+    PK_HIP(c, hipExtModuleLaunchKernel(c->fn[k], grid * PK_BLOCK, 1, 1, PK_BLOCK, 1, 1, shape.lds_bytes, st, nullptr, config,
                                        ev.a, ev.b, 0));
     c->pending[k].push_back(ev);
     return 0;
   }
-  PK_HIP(c, hipModuleLaunchKernel(c->fn[k], grid, 1, 1, PK_BLOCK, 1, 1, (unsigned)lds_bytes, st, nullptr, config));
+  PK_HIP(c, hipModuleLaunchKernel(c->fn[k], grid, 1, 1, PK_BLOCK, 1, 1, (unsigned)shape.lds_bytes, st, nullptr, config));
   return 0;
 }
 
-int launch(pk_ctx* c, int k, PkArgs& A, unsigned grid, size_t lds_bytes, hipStream_t st) {
+int launch(pk_ctx* c, int k, PkArgs& A, hipStream_t st, int64_t n_flat = 0) {
   // pk_xall runs the values role of a WIDE phase with its dynamics passes inside the values wave: wrong f / grad / g for
   // some models and GPU memory faults (round 5, an open defect on that kernel's SGPR-spill path).
   // Every route to it -- the two-launch cycle, a profiled context, pk_set_option("xpart_single", 0), the x-part of a
@@ -376,26 +375,23 @@ int launch(pk_ctx* c, int k, PkArgs& A, unsigned grid, size_t lds_bytes, hipStre
   if (k == K_XALL && c->md.wide)
     return fail(c, 27, "pk_xall is not offered for a model with a wide phase (open defect of its sequential values role, DESIGN.md "
                        "section 11): use the one-launch cycle / the callbacks of an unprofiled context (the default)");
-  return launch_raw(c, k, &A, args_bytes(c), grid, lds_bytes, st);
+  return launch_raw(c, k, &A, args_bytes(c), shape_of(c, k, n_flat), st);
 }
-
-unsigned tile_blocks(const pk_ctx* c) { return (unsigned)((c->n_tiles + PK_WAVES_PER_BLOCK - 1) / PK_WAVES_PER_BLOCK); }
-// pk_hess: edge and reduction workgroups + one workgroup per tile block -- per PASS of a block for a model evaluated in groups
-// whose code object runs the passes as workgroups of their own (md.hess_subs, codegen.py)
-unsigned hess_grid(const pk_ctx* c) { return tile_blocks(c) * (c->md.hess_subs > 0 ? (unsigned)c->md.hess_subs : 1u) + 2u; }
 
 int prepass(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f, bool write_f, hipStream_t st) {
   PkArgs A = base_args(c, d_x, d_lam, sigma);
   A.o_f = d_f;
-  int rc = launch(c, K_INT, A, tile_blocks(c), 0, st);
+  int rc = launch(c, K_INT, A, st);
   if (rc) return rc;
   A.flags |= F_FIN_INT | (write_f ? F_WRITE_F : 0);
-  return launch(c, K_FIN, A, 1, 0, st);
+  return launch(c, K_FIN, A, st);
 }
 
-// pk_xall's launch shape: one wave per tile, or -- split launch -- two waves (of two workgroups) per tile
-unsigned xall_blocks(const pk_ctx* c) { return (c->split_xall ? 2u : 1u) * tile_blocks(c) + 1u; }
-int xall_flags(const pk_ctx* c) { return c->split_xall ? F_SPLIT : 0; }
+// The integral pre-pass in front of a callback whose system functions are nonlinear in the integrals (`needed`: the callback's
+// pk_model_desc.prepass_*), unless the caller reduces the integrals itself (a shard, pk_set_shard).
+int prepass_if(pk_ctx* c, int32_t needed, const double* d_x, const double* d_lam, double sigma, hipStream_t st) {
+  return (needed && !c->external_prepass) ? prepass(c, d_x, d_lam, sigma, c->d_f, false, st) : 0;
+}
 
 // the cycle as ONE launch (pk_cycle): [edge J | edge H | finalize | tile slots: x block(s) + Hessian block per group]
 // (d_lam == NULL: the x-part alone -- the Hessian workgroups of the grid leave at once)
@@ -413,26 +409,16 @@ int enqueue_single_launch_cycle(pk_ctx* c, const double* d_x, const double* d_la
   A.n_items2 = (layout & 2) ? c->n_items_hessc : c->n_items_hess;
   if (layout & 1) A.flags |= F_COMPACT_J;
   if (layout & 2) A.flags |= F_COMPACT_H;
-  A.flags |= F_FIN_INT | F_WRITE_F | F_FIN_GRAD | xall_flags(c);
+  A.flags |= F_FIN_INT | F_WRITE_F | F_FIN_GRAD | (c->split_xall ? F_SPLIT : 0);
   if (c->xc_inline && c->xc_world > 1) {      // sharded: the sums over the ranks are exchanged inside this launch
     A.flags |= F_XCHG;
     A.xc_box = (unsigned long long* const*)c->xc_box; A.xc_idx = c->xc_idx;
     A.xc_world = c->xc_world; A.xc_rank = c->xc_rank; A.xc_epoch = 0; A.xc_nsh = c->xc_nsh; A.xc_stride = c->xc_stride;
   }      // (xc_epoch = 0: the cycle number is kept in device memory, so these arguments never change -> graph-replayable)
-  size_t dbl = PK_WAVES_PER_BLOCK * (size_t)(c->md.lds_x > c->md.lds_h ? c->md.lds_x : c->md.lds_h);
-  if (dbl < (size_t)c->md.ne_j) dbl = (size_t)c->md.ne_j;
-  if (dbl < (size_t)c->md.ne_h) dbl = (size_t)c->md.ne_h;
-  if (layout & 1) {      // (tile_jacc stages in the x-part's rows: lds_x >= lds_jc by construction, codegen.py)
-    if (dbl < (size_t)c->md.ne_jc) dbl = (size_t)c->md.ne_jc;
-  }
-  if (layout & 2) {
-    if (dbl < PK_WAVES_PER_BLOCK * (size_t)c->md.lds_g) dbl = PK_WAVES_PER_BLOCK * (size_t)c->md.lds_g;
-    if (dbl < (size_t)c->md.ne_hc) dbl = (size_t)c->md.ne_hc;
-  }
-  // workgroups per tile block: [Jacobian | values | Hessian] (x-part split) or [x-part | Hessian]; a model evaluated in groups:
-  // one per pass of the Jacobian / Hessian role beside the values workgroup (md.cycle_subs, codegen.py)
-  const unsigned per_group = c->md.cycle_subs > 0 ? (unsigned)c->md.cycle_subs : (c->split_xall ? 3u : 2u);
-  const unsigned grid = tile_blocks(c) * per_group + 3u;
+  // (the compact layouts: pk_cyclec, the same launch compiled with their roles -- a kernel of its own so that pk_cycle's
+  //  register count stays what the reference layouts need)
+  const int k = layout ? K_CYCLEC : K_CYCLE;
+  const PkLaunchShape shape = shape_of(c, k, 0, layout);
   // pk_cycle's kernarg segment: the scalars a tile wave needs first (preloaded into SGPRs), then the PkArgs
   struct CycleArgs {
     const PkTile* tile;
@@ -440,11 +426,9 @@ int enqueue_single_launch_cycle(pk_ctx* c, const double* d_x, const double* d_la
     PkArgs A;
   } K;
   static_assert(offsetof(CycleArgs, A) == PK_CYCLE_ARGS_OFFSET, "layout of pk_cycle's kernel arguments");
-  K.tile = A.tile; K.n_tiles = A.n_tiles; K.flags = A.flags; K.grid = (int32_t)grid; K.pad = 0;
+  K.tile = A.tile; K.n_tiles = A.n_tiles; K.flags = A.flags; K.grid = (int32_t)shape.grid; K.pad = 0;
   std::memcpy(static_cast<void*>(&K.A), &A, args_bytes(c));
-  // (the compact layouts: pk_cyclec, the same launch compiled with their roles -- a kernel of its own so that pk_cycle's
-  //  register count stays what the reference layouts need)
-  return launch_raw(c, layout ? K_CYCLEC : K_CYCLE, &K, offsetof(CycleArgs, A) + args_bytes(c), grid, sizeof(double) * dbl, st);
+  return launch_raw(c, k, &K, offsetof(CycleArgs, A) + args_bytes(c), shape, st);
 }
 
 int enqueue_fused_cycle(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f, double* d_grad,
@@ -456,19 +440,15 @@ int enqueue_fused_cycle(pk_ctx* c, const double* d_x, const double* d_lam, doubl
   A.o_f = d_f; A.o_grad = d_grad; A.o_g = d_g; A.o_jac = d_jac;
   A.items = (const PkItem*)c->d_items_jac;
   A.n_items = c->n_items_jac;
-  size_t lds = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_x;
-  if (lds < sizeof(double) * (size_t)c->md.ne_j) lds = sizeof(double) * (size_t)c->md.ne_j;
-  A.flags |= xall_flags(c);
-  if ((rc = launch(c, K_XALL, A, xall_blocks(c), lds, st))) return rc;
+  A.flags |= (c->split_xall ? F_SPLIT : 0);
+  if ((rc = launch(c, K_XALL, A, st))) return rc;
   // pk_hess's boundary workgroup also performs pk_fin's reductions (f, shared gradient slots)
   PkArgs H = base_args(c, d_x, d_lam, sigma);
   H.o_f = d_f; H.o_grad = d_grad; H.o_hess = d_hess;
   H.items = (const PkItem*)c->d_items_hess;
   H.n_items = c->n_items_hess;
-  H.flags |= F_FIN_INT | F_WRITE_F | F_FIN_GRAD | xall_flags(c);
-  lds = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_h;
-  if (lds < sizeof(double) * (size_t)c->md.ne_h) lds = sizeof(double) * (size_t)c->md.ne_h;
-  return launch(c, K_HESS, H, hess_grid(c), lds, st);
+  H.flags |= F_FIN_INT | F_WRITE_F | F_FIN_GRAD | (c->split_xall ? F_SPLIT : 0);
+  return launch(c, K_HESS, H, st);
 }
 
 hipStream_t pick(pk_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
@@ -752,6 +732,35 @@ int stage_upload(pk_ctx* c, double* const bufs[2], hipEvent_t const evs[2], uint
   return 0;
 }
 
+// ---- the host-buffer form of an entry point: upload x (and lambda), the device-pointer entry point, download, synchronize
+int host_ready(pk_ctx* c, bool buffers) {
+  const int rc = ready(c);
+  return rc ? rc : buffers ? 0 : fail(c, 60, "null host buffer");
+}
+struct Download { double* host; const double* dev; size_t count; };
+
+// lambda == NULL: x alone goes up.  staged: the inputs go through the double-buffered pinned staging buffers of the host shim
+// (pk_eval_cycle) instead of a copy from the caller's arrays.  handoff: errors 97 of the fused cycle are reported.
+template <class Eval>
+int host_eval(pk_ctx* c, const double* x, const double* lambda, std::initializer_list<Download> results, bool handoff, Eval eval,
+              bool staged = false) {
+  int rc;
+  PK_HIP(c, hipSetDevice(c->device));
+  c->x_valid = false;      // the context's x and result buffers now hold another evaluation
+  if (staged) {
+    if ((rc = stage_upload(c, c->h_xs, c->ev_xs, c->xs_seq, c->xbuf, x, c->d_x, (size_t)c->n, nullptr))) return rc;
+    if ((rc = stage_upload(c, c->h_lams, c->ev_lams, c->lams_seq, c->lambuf, lambda, c->d_lam, (size_t)c->m, nullptr))) return rc;
+  } else {
+    PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    if (lambda) PK_HIP(c, hipMemcpyAsync(c->d_lam, lambda, sizeof(double) * (size_t)c->m, hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = eval())) return rc;
+  for (const Download& r : results)
+    PK_HIP(c, hipMemcpyAsync(r.host, r.dev, sizeof(double) * r.count, hipMemcpyDeviceToHost, c->stream));
+  PK_HIP(c, hipStreamSynchronize(c->stream));
+  return handoff ? handoff_check(c) : 0;
+}
+
 }  // namespace
 
 extern "C" int pk_eval_xpart_dev(pk_ctx* c, const double* d_x, double* d_f, double* d_grad, double* d_g, double* d_jac, void* stream);
@@ -834,15 +843,16 @@ int pk_load_model(pk_ctx* c, const void* code_object, size_t len, const pk_model
   if (md->max_phases < 0 || md->max_phases > PK_HOST_MAX_PHASES || md->n_phase > (md->max_phases > 0 ? md->max_phases : 8))
     return fail(c, 24, "pk_load_model: %d phases, code object compiled for %d (the library passes at most %d phase records in "
                        "the kernel arguments)", md->n_phase, md->max_phases > 0 ? md->max_phases : 8, PK_HOST_MAX_PHASES);
-  // what a launch will ask for (launch_raw): the model's staging rows of the workgroup's waves + their table blocks -- the
-  // same bytes pockit_amd.codegen.ModelSource.launch_lds_bytes counts when it chooses the group size
-  const size_t lds_max = 160 * 1024;
-  const size_t tab = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)(2 * md->tab_cap + 2 * PK_WAVE + md->tab_cap / 2);
-  const size_t need[5] = {(size_t)md->lds_g, (size_t)md->lds_j, (size_t)md->lds_h, (size_t)md->lds_x, (size_t)md->lds_jc};
-  for (size_t v : need)
-    if (v * PK_WAVES_PER_BLOCK * sizeof(double) + tab > lds_max)
-      return fail(c, 21, "pk_load_model: model needs %zu bytes of LDS per workgroup (> 160 KiB)",
-                  v * PK_WAVES_PER_BLOCK * sizeof(double) + tab);
+  // what the launches will ask for (pk_launch.h); pk_cyclec with every compact role the descriptor has expressions for, which
+  // needs no less than any other layout.  Not pk_aux and pk_err: a model without outer-product blocks / a caller without mesh
+  // error tables never launches them (errors 22, 72).
+  PkLaunchFacts p;
+  p.layout = (md->ne_jc > 0 ? 1 : 0) | (md->ne_hc > 0 ? 2 : 0);
+  for (int k = 0; k < K_COUNT; ++k) {
+    const size_t lds = pk_launch_shape(k, *md, p).lds_bytes;
+    if (k != K_AUX && k != K_ERR && lds > PK_LDS_LIMIT)
+      return fail(c, 21, "pk_load_model: model needs %zu bytes of LDS per workgroup (> 160 KiB)", lds);
+  }
   c->have_model = true;
   return 0;
 }
@@ -1009,7 +1019,7 @@ int pk_eval_f_from_integrals_dev(pk_ctx* c, const double* d_x, double* d_f, void
   PkArgs A = base_args(c, d_x, nullptr, 0.0);
   A.o_f = d_f;
   A.flags |= F_WRITE_F;
-  return launch(c, K_FIN, A, 1, 0, pick(c, stream));
+  return launch(c, K_FIN, A, pick(c, stream));
 }
 
 int pk_set_shard(pk_ctx* c, int secondary, int external_prepass, double* d_integrals) {
@@ -1026,12 +1036,12 @@ int pk_eval_grad_dev(pk_ctx* c, const double* d_x, double* d_grad, void* stream)
   if (rc) return rc;
   if (c->has_big) return eval_one_via_xpart(c, d_x, 1, d_grad, stream);
   hipStream_t st = pick(c, stream);
-  if (c->md.prepass_grad && !c->external_prepass && (rc = prepass(c, d_x, nullptr, 0.0, c->d_f, false, st))) return rc;
+  if ((rc = prepass_if(c, c->md.prepass_grad, d_x, nullptr, 0.0, st))) return rc;
   PkArgs A = base_args(c, d_x, nullptr, 0.0);
   A.o_grad = d_grad;
-  if ((rc = launch(c, K_GRAD, A, tile_blocks(c), 0, st))) return rc;
+  if ((rc = launch(c, K_GRAD, A, st))) return rc;
   A.flags |= F_FIN_GRAD;
-  return launch(c, K_FIN, A, 1, 0, st);
+  return launch(c, K_FIN, A, st);
 }
 
 int pk_eval_g_dev(pk_ctx* c, const double* d_x, double* d_g, void* stream) {
@@ -1039,10 +1049,10 @@ int pk_eval_g_dev(pk_ctx* c, const double* d_x, double* d_g, void* stream) {
   if (rc) return rc;
   if (c->has_big) return eval_one_via_xpart(c, d_x, 2, d_g, stream);
   hipStream_t st = pick(c, stream);
-  if (c->md.prepass_g && !c->external_prepass && (rc = prepass(c, d_x, nullptr, 0.0, c->d_f, false, st))) return rc;
+  if ((rc = prepass_if(c, c->md.prepass_g, d_x, nullptr, 0.0, st))) return rc;
   PkArgs A = base_args(c, d_x, nullptr, 0.0);
   A.o_g = d_g;
-  return launch(c, K_G, A, tile_blocks(c) + 1, sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_g, st);
+  return launch(c, K_G, A, st);
 }
 
 int pk_eval_jac_dev(pk_ctx* c, const double* d_x, double* d_vals, void* stream) {
@@ -1050,14 +1060,12 @@ int pk_eval_jac_dev(pk_ctx* c, const double* d_x, double* d_vals, void* stream) 
   if (rc) return rc;
   if (c->has_big) return eval_one_via_xpart(c, d_x, 3, d_vals, stream);
   hipStream_t st = pick(c, stream);
-  if (c->md.prepass_jac && !c->external_prepass && (rc = prepass(c, d_x, nullptr, 0.0, c->d_f, false, st))) return rc;
+  if ((rc = prepass_if(c, c->md.prepass_jac, d_x, nullptr, 0.0, st))) return rc;
   PkArgs A = base_args(c, d_x, nullptr, 0.0);
   A.o_jac = d_vals;
   A.items = (const PkItem*)c->d_items_jac;
   A.n_items = c->n_items_jac;
-  size_t lds = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_j;
-  if (lds < sizeof(double) * (size_t)c->md.ne_j) lds = sizeof(double) * (size_t)c->md.ne_j;
-  return launch(c, K_JAC, A, tile_blocks(c) + 1, lds, st);
+  return launch(c, K_JAC, A, st);
 }
 
 int pk_eval_hess_dev(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_vals, void* stream) {
@@ -1065,25 +1073,22 @@ int pk_eval_hess_dev(pk_ctx* c, const double* d_x, const double* d_lam, double s
   if (rc) return rc;
   if (!d_lam) return fail(c, 50, "pk_eval_hess: lambda is required");
   hipStream_t st = pick(c, stream);
-  if (c->md.prepass_hess && !c->external_prepass && (rc = prepass(c, d_x, d_lam, sigma, c->d_f, false, st))) return rc;
+  if ((rc = prepass_if(c, c->md.prepass_hess, d_x, d_lam, sigma, st))) return rc;
   PkArgs A = base_args(c, d_x, d_lam, sigma);
   A.o_hess = d_vals;
   A.items = (const PkItem*)c->d_items_hess;
   A.n_items = c->n_items_hess;
-  size_t lds = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_h;
-  if (lds < sizeof(double) * (size_t)c->md.ne_h) lds = sizeof(double) * (size_t)c->md.ne_h;
-  if ((rc = launch(c, K_HESS, A, hess_grid(c), lds, st))) return rc;
+  if ((rc = launch(c, K_HESS, A, st))) return rc;
   if (c->n_outer > 0) {   // objective / system constraints nonlinear in the integrals: outer-product blocks
     PkArgs X = base_args(c, d_x, d_lam, sigma);
     X.o_hess = d_vals;
     X.items = (const PkItem*)c->d_items_aux;
     X.n_items = c->n_items_aux;
-    if ((rc = launch(c, K_AUX, X, tile_blocks(c) + 1, sizeof(double) * (size_t)(c->md.ne_a > 0 ? c->md.ne_a : 1), st))) return rc;
+    if ((rc = launch(c, K_AUX, X, st))) return rc;
     // a shard stops here: its auxiliary buffer holds the entries of ITS nodes, the caller sums the buffers over the
     // ranks and has the primary rank form the blocks (pk_eval_outer_dev)
     if (c->external_prepass) return 0;
-    const unsigned grid = (unsigned)(c->n_outer < 4096 ? c->n_outer : 4096);
-    return launch(c, K_OUTER, X, grid, 0, st);
+    return launch(c, K_OUTER, X, st);
   }
   return 0;
 }
@@ -1107,8 +1112,7 @@ int pk_eval_outer_dev(pk_ctx* c, const double* d_aux_sum, double* d_vals, void* 
   PkArgs X = base_args(c, nullptr, nullptr, 0.0);
   X.o_hess = d_vals;
   X.o_aux = const_cast<double*>(d_aux_sum);
-  const unsigned grid = (unsigned)(c->n_outer < 4096 ? c->n_outer : 4096);
-  return launch(c, K_OUTER, X, grid, 0, pick(c, stream));
+  return launch(c, K_OUTER, X, pick(c, stream));
 }
 
 // compact (coalesced) Hessian of the Lagrangian: one value per distinct (row, col) class of a node
@@ -1118,14 +1122,12 @@ int pk_eval_hessc_dev(pk_ctx* c, const double* d_x, const double* d_lam, double 
   if (!d_lam) return fail(c, 50, "pk_eval_hessc: lambda is required");
   if (c->nnz_Hc <= 0) return fail(c, 51, "pk_eval_hessc: no compact Hessian layout was supplied to pk_set_problem");
   hipStream_t st = pick(c, stream);
-  if (c->md.prepass_hess && !c->external_prepass && (rc = prepass(c, d_x, d_lam, sigma, c->d_f, false, st))) return rc;
+  if ((rc = prepass_if(c, c->md.prepass_hess, d_x, d_lam, sigma, st))) return rc;
   PkArgs A = base_args(c, d_x, d_lam, sigma);
   A.o_hess = d_vals;
   A.items = (const PkItem*)c->d_items_hessc;
   A.n_items = c->n_items_hessc;
-  size_t lds = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_g;      // the tile's multiplier rows, [state][row]
-  if (lds < sizeof(double) * (size_t)c->md.ne_hc) lds = sizeof(double) * (size_t)c->md.ne_hc;
-  return launch(c, K_HESSC, A, tile_blocks(c) * (c->md.hessc_subs > 0 ? (unsigned)c->md.hessc_subs : 1u) + 1, lds, st);
+  return launch(c, K_HESSC, A, st);
 }
 
 // compact (coalesced) Jacobian: dense-column entries of the dynamics contracted with the integration block first
@@ -1134,27 +1136,17 @@ int pk_eval_jacc_dev(pk_ctx* c, const double* d_x, double* d_vals, void* stream)
   if (rc) return rc;
   if (c->nnz_Jc <= 0) return fail(c, 52, "pk_eval_jacc: no compact Jacobian layout was supplied to pk_set_problem");
   hipStream_t st = pick(c, stream);
-  if (c->md.prepass_jac && !c->external_prepass && (rc = prepass(c, d_x, nullptr, 0.0, c->d_f, false, st))) return rc;
+  if ((rc = prepass_if(c, c->md.prepass_jac, d_x, nullptr, 0.0, st))) return rc;
   PkArgs A = base_args(c, d_x, nullptr, 0.0);
   A.o_jac = d_vals;
   A.items = (const PkItem*)c->d_items_jacc;
   A.n_items = c->n_items_jacc;
-  size_t lds = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_jc;
-  if (lds < sizeof(double) * (size_t)c->md.ne_jc) lds = sizeof(double) * (size_t)c->md.ne_jc;
-  return launch(c, K_JACC, A, tile_blocks(c) * (c->md.jacc_subs > 0 ? (unsigned)c->md.jacc_subs : 1u) + 1, lds, st);
+  return launch(c, K_JACC, A, st);
 }
 
 int pk_eval_jacc(pk_ctx* c, const double* x, double* vals) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (!x || !vals) return fail(c, 60, "null host buffer");
-  PK_HIP(c, hipSetDevice(c->device));
-  c->x_valid = false;
-  PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = pk_eval_jacc_dev(c, c->d_x, c->d_Jc, nullptr))) return rc;
-  PK_HIP(c, hipMemcpyAsync(vals, c->d_Jc, sizeof(double) * (size_t)c->nnz_Jc, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  const int rc = host_ready(c, x && vals);
+  return rc ? rc : host_eval(c, x, nullptr, {{vals, c->d_Jc, (size_t)c->nnz_Jc}}, false, [&] { return pk_eval_jacc_dev(c, c->d_x, c->d_Jc, nullptr); });
 }
 
 // ---------------------------------------------------------------- device-resident CSR hand-off
@@ -1218,9 +1210,7 @@ int pk_gather_csr_dev(pk_ctx* c, int which, const double* d_triplets, double* d_
   const auto& m = c->csr[which];
   PkArgs A = base_args(c, nullptr, nullptr, 0.0);
   A.csr_in = d_triplets; A.csr_seg = m.d_seg; A.csr_perm = m.d_perm; A.csr_out = d_csr; A.n_csr = (int32_t)m.n_unique;
-  unsigned grid = (unsigned)((m.n_unique + PK_BLOCK - 1) / PK_BLOCK);
-  if (grid > 4096) grid = 4096;
-  return launch(c, K_CSR, A, grid, 0, pick(c, stream));
+  return launch(c, K_CSR, A, pick(c, stream), m.n_unique);
 }
 
 int pk_eval_jac_csr_dev(pk_ctx* c, const double* d_x, double* d_csr, void* stream) {
@@ -1247,34 +1237,19 @@ int pk_eval_hess_csr_dev(pk_ctx* c, const double* d_x, const double* d_lam, doub
 }
 
 int pk_eval_jac_csr(pk_ctx* c, const double* x, double* vals) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (!x || !vals) return fail(c, 60, "null host buffer");
-  const int jm = c->csr[3].n_unique > 0 ? 3 : 0;      // (both maps fill the same CSR entries)
-  if (c->csr[jm].n_unique == 0) return fail(c, 84, "pk_eval_jac_csr: call pk_set_csr_map first");
-  PK_HIP(c, hipSetDevice(c->device));
-  c->x_valid = false;
-  PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = pk_eval_jac_csr_dev(c, c->d_x, c->csr[jm].d_vals, nullptr))) return rc;
-  PK_HIP(c, hipMemcpyAsync(vals, c->csr[jm].d_vals, sizeof(double) * (size_t)c->csr[jm].n_unique, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  if (const int rc = host_ready(c, x && vals)) return rc;
+  const pk_ctx::CsrMap& m = c->csr[c->csr[3].n_unique > 0 ? 3 : 0];      // (both maps fill the same CSR entries)
+  if (m.n_unique == 0) return fail(c, 84, "pk_eval_jac_csr: call pk_set_csr_map first");
+  return host_eval(c, x, nullptr, {{vals, m.d_vals, (size_t)m.n_unique}}, false,
+                   [&] { return pk_eval_jac_csr_dev(c, c->d_x, m.d_vals, nullptr); });
 }
 
 int pk_eval_hess_csr(pk_ctx* c, const double* x, const double* lambda, double sigma, double* vals) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (!x || !lambda || !vals) return fail(c, 60, "null host buffer");
-  const int hm = c->csr[2].n_unique > 0 ? 2 : 1;      // (both maps fill the same CSR entries)
-  if (c->csr[hm].n_unique == 0) return fail(c, 84, "pk_eval_hess_csr: call pk_set_csr_map first");
-  PK_HIP(c, hipSetDevice(c->device));
-  c->x_valid = false;
-  PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-  PK_HIP(c, hipMemcpyAsync(c->d_lam, lambda, sizeof(double) * (size_t)c->m, hipMemcpyHostToDevice, c->stream));
-  if ((rc = pk_eval_hess_csr_dev(c, c->d_x, c->d_lam, sigma, c->csr[hm].d_vals, nullptr))) return rc;
-  PK_HIP(c, hipMemcpyAsync(vals, c->csr[hm].d_vals, sizeof(double) * (size_t)c->csr[hm].n_unique, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  if (const int rc = host_ready(c, x && lambda && vals)) return rc;
+  const pk_ctx::CsrMap& m = c->csr[c->csr[2].n_unique > 0 ? 2 : 1];      // (both maps fill the same CSR entries)
+  if (m.n_unique == 0) return fail(c, 84, "pk_eval_hess_csr: call pk_set_csr_map first");
+  return host_eval(c, x, lambda, {{vals, m.d_vals, (size_t)m.n_unique}}, false,
+                   [&] { return pk_eval_hess_csr_dev(c, c->d_x, c->d_lam, sigma, m.d_vals, nullptr); });
 }
 
 // ---------------------------------------------------------------- mesh error estimation
@@ -1286,7 +1261,7 @@ int pk_set_mesh_error_tables(pk_ctx* c, const void* intervals, int32_t n_interva
     return fail(c, 70, "pk_set_mesh_error_tables: empty tables");
   if (n_groups % PK_WAVES_PER_BLOCK)
     return fail(c, 71, "pk_set_mesh_error_tables: wave groups must be padded to a multiple of %d per phase", PK_WAVES_PER_BLOCK);
-  if (((size_t)c->md.lds_e / PK_WAVE) * 264 * sizeof(double) > 160 * 1024)
+  if (shape_of(c, K_ERR).lds_bytes > PK_LDS_LIMIT)
     return fail(c, 72, "pk_set_mesh_error_tables: model needs more than 160 KiB of LDS per workgroup");
   // host-side validation of everything the kernel indexes with (a faulting kernel can take the node down)
   const PkErrIv* iv = (const PkErrIv*)intervals;
@@ -1366,37 +1341,18 @@ int pk_eval_mesh_error_dev(pk_ctx* c, const double* d_x, double* d_T, double* d_
   A.o_errT = d_T;
   A.o_errI = d_I;
   A.big_stage = c->d_err_stage; A.big_row = c->err_row; A.big_slot = c->err_slot;
-  // (lds_e = 64 (2 n_x + n_u) doubles per wave; a workgroup-wide interval stages rows of 264 doubles)
-  return launch(c, K_ERR, A, (unsigned)(c->n_erriv / PK_WAVES_PER_BLOCK),
-                sizeof(double) * ((size_t)c->md.lds_e / PK_WAVE) * 264, pick(c, stream));
+  return launch(c, K_ERR, A, pick(c, stream));
 }
 
 int pk_eval_mesh_error(pk_ctx* c, const double* x, double* T, double* I) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (!x || !T || !I) return fail(c, 60, "null host buffer");
-  PK_HIP(c, hipSetDevice(c->device));
-  c->x_valid = false;
-  PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = pk_eval_mesh_error_dev(c, c->d_x, c->d_errT, c->d_errI, nullptr))) return rc;
-  PK_HIP(c, hipMemcpyAsync(T, c->d_errT, sizeof(double) * (size_t)c->n_err_out, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipMemcpyAsync(I, c->d_errI, sizeof(double) * (size_t)c->n_err_out, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  const int rc = host_ready(c, x && T && I);
+  return rc ? rc : host_eval(c, x, nullptr, {{T, c->d_errT, (size_t)c->n_err_out}, {I, c->d_errI, (size_t)c->n_err_out}}, false,
+                             [&] { return pk_eval_mesh_error_dev(c, c->d_x, c->d_errT, c->d_errI, nullptr); });
 }
 
 int pk_eval_hessc(pk_ctx* c, const double* x, const double* lambda, double sigma, double* vals) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (!x || !lambda || !vals) return fail(c, 60, "null host buffer");
-  PK_HIP(c, hipSetDevice(c->device));
-  c->x_valid = false;
-  PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-  PK_HIP(c, hipMemcpyAsync(c->d_lam, lambda, sizeof(double) * (size_t)c->m, hipMemcpyHostToDevice, c->stream));
-  if ((rc = pk_eval_hessc_dev(c, c->d_x, c->d_lam, sigma, c->d_Hc, nullptr))) return rc;
-  PK_HIP(c, hipMemcpyAsync(vals, c->d_Hc, sizeof(double) * (size_t)c->nnz_Hc, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  const int rc = host_ready(c, x && lambda && vals);
+  return rc ? rc : host_eval(c, x, lambda, {{vals, c->d_Hc, (size_t)c->nnz_Hc}}, false, [&] { return pk_eval_hessc_dev(c, c->d_x, c->d_lam, sigma, c->d_Hc, nullptr); });
 }
 
 int pk_exchange_sums_dev(pk_ctx* c, const double* d_x, double* d_grad, double* d_f, int epoch, int write_f, void* stream);
@@ -1530,13 +1486,11 @@ int pk_eval_xpart_dev(pk_ctx* c, const double* d_x, double* d_f, double* d_grad,
   A.o_f = d_f; A.o_grad = d_grad; A.o_g = d_g; A.o_jac = d_jac;
   A.items = (const PkItem*)c->d_items_jac;
   A.n_items = c->n_items_jac;
-  size_t lds = sizeof(double) * PK_WAVES_PER_BLOCK * (size_t)c->md.lds_x;
-  if (lds < sizeof(double) * (size_t)c->md.ne_j) lds = sizeof(double) * (size_t)c->md.ne_j;
-  A.flags |= xall_flags(c);
-  if ((rc = launch(c, K_XALL, A, xall_blocks(c), lds, st))) return rc;
+  A.flags |= (c->split_xall ? F_SPLIT : 0);
+  if ((rc = launch(c, K_XALL, A, st))) return rc;
   // (a shard of a model nonlinear in the integrals: the caller has summed the integrals over the ranks, they stay as they are)
   A.flags |= ((needs_I && c->external_prepass) ? 0 : (F_FIN_INT | F_WRITE_F)) | F_FIN_GRAD;
-  return launch(c, K_FIN, A, 1, 0, st);
+  return launch(c, K_FIN, A, st);
 }
 
 // Which layouts pk_eval_cycle_dev writes into d_jac / d_hess: 0 the reference's triplets (default), 1 the compact layout
@@ -1590,54 +1544,39 @@ int pk_wait_idle(pk_ctx* c, void* stream) {
 }
 
 // ---------------------------------------------------------------- host-buffer API
-#define PK_HOST_EVAL(IN_COPY, CALL, D_OUT, OUT, COUNT)                                                      \
-  int rc = ready(c);                                                                                        \
-  if (rc) return rc;                                                                                        \
-  if (!x || !(OUT)) return fail(c, 60, "null host buffer");                                                 \
-  PK_HIP(c, hipSetDevice(c->device));                                                                       \
-  c->x_valid = false; /* the context's x and result buffers now hold another evaluation */                  \
-  PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));    \
-  IN_COPY;                                                                                                  \
-  if ((rc = (CALL))) return rc;                                                                             \
-  PK_HIP(c, hipMemcpyAsync((OUT), (D_OUT), sizeof(double) * (size_t)(COUNT), hipMemcpyDeviceToHost, c->stream)); \
-  PK_HIP(c, hipStreamSynchronize(c->stream));                                                               \
-  return handoff_check(c);
-
-int pk_eval_f(pk_ctx* c, const double* x, double* f) { PK_HOST_EVAL((void)0, pk_eval_f_dev(c, c->d_x, c->d_f, nullptr), c->d_f, f, 1) }
-
-int pk_eval_grad(pk_ctx* c, const double* x, double* grad) {
-  PK_HOST_EVAL((void)0, pk_eval_grad_dev(c, c->d_x, c->d_grad, nullptr), c->d_grad, grad, c->n)
+int pk_eval_f(pk_ctx* c, const double* x, double* f) {
+  const int rc = host_ready(c, x && f);
+  return rc ? rc : host_eval(c, x, nullptr, {{f, c->d_f, 1}}, true, [&] { return pk_eval_f_dev(c, c->d_x, c->d_f, nullptr); });
 }
 
-int pk_eval_g(pk_ctx* c, const double* x, double* g) { PK_HOST_EVAL((void)0, pk_eval_g_dev(c, c->d_x, c->d_g, nullptr), c->d_g, g, c->m) }
+int pk_eval_grad(pk_ctx* c, const double* x, double* grad) {
+  const int rc = host_ready(c, x && grad);
+  return rc ? rc : host_eval(c, x, nullptr, {{grad, c->d_grad, (size_t)c->n}}, true, [&] { return pk_eval_grad_dev(c, c->d_x, c->d_grad, nullptr); });
+}
+
+int pk_eval_g(pk_ctx* c, const double* x, double* g) {
+  const int rc = host_ready(c, x && g);
+  return rc ? rc : host_eval(c, x, nullptr, {{g, c->d_g, (size_t)c->m}}, true, [&] { return pk_eval_g_dev(c, c->d_x, c->d_g, nullptr); });
+}
 
 int pk_eval_jac(pk_ctx* c, const double* x, double* vals) {
-  PK_HOST_EVAL((void)0, pk_eval_jac_dev(c, c->d_x, c->d_J, nullptr), c->d_J, vals, c->nnz_J)
+  const int rc = host_ready(c, x && vals);
+  return rc ? rc : host_eval(c, x, nullptr, {{vals, c->d_J, (size_t)c->nnz_J}}, true, [&] { return pk_eval_jac_dev(c, c->d_x, c->d_J, nullptr); });
 }
 
 int pk_eval_hess(pk_ctx* c, const double* x, const double* lambda, double sigma, double* vals) {
   if (c && !lambda) return fail(c, 50, "pk_eval_hess: lambda is required");
-  PK_HOST_EVAL(PK_HIP(c, hipMemcpyAsync(c->d_lam, lambda, sizeof(double) * (size_t)c->m, hipMemcpyHostToDevice, c->stream)),
-               pk_eval_hess_dev(c, c->d_x, c->d_lam, sigma, c->d_H, nullptr), c->d_H, vals, c->nnz_H)
+  const int rc = host_ready(c, x && vals);
+  return rc ? rc : host_eval(c, x, lambda, {{vals, c->d_H, (size_t)c->nnz_H}}, true, [&] { return pk_eval_hess_dev(c, c->d_x, c->d_lam, sigma, c->d_H, nullptr); });
 }
 
 int pk_eval_cycle(pk_ctx* c, const double* x, const double* lambda, double sigma, double* f, double* grad, double* g,
                   double* jac, double* hess) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (!x || !lambda || !f || !grad || !g || !jac || !hess) return fail(c, 60, "null host buffer");
-  PK_HIP(c, hipSetDevice(c->device));
-  c->x_valid = false;
-  if ((rc = stage_upload(c, c->h_xs, c->ev_xs, c->xs_seq, c->xbuf, x, c->d_x, (size_t)c->n, nullptr))) return rc;
-  if ((rc = stage_upload(c, c->h_lams, c->ev_lams, c->lams_seq, c->lambuf, lambda, c->d_lam, (size_t)c->m, nullptr))) return rc;
-  if ((rc = pk_eval_cycle_dev(c, c->d_x, c->d_lam, sigma, c->d_f, c->d_grad, c->d_g, c->d_J, c->d_H, nullptr))) return rc;
-  PK_HIP(c, hipMemcpyAsync(f, c->d_f, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipMemcpyAsync(grad, c->d_grad, sizeof(double) * (size_t)c->n, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipMemcpyAsync(g, c->d_g, sizeof(double) * (size_t)c->m, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipMemcpyAsync(jac, c->d_J, sizeof(double) * (size_t)c->nnz_J, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipMemcpyAsync(hess, c->d_H, sizeof(double) * (size_t)c->nnz_H, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return handoff_check(c);
+  if (const int rc = host_ready(c, x && lambda && f && grad && g && jac && hess)) return rc;
+  return host_eval(c, x, lambda, {{f, c->d_f, 1}, {grad, c->d_grad, (size_t)c->n}, {g, c->d_g, (size_t)c->m},
+                                  {jac, c->d_J, (size_t)c->nnz_J}, {hess, c->d_H, (size_t)c->nnz_H}}, true,
+                   [&] { return pk_eval_cycle_dev(c, c->d_x, c->d_lam, sigma, c->d_f, c->d_grad, c->d_g, c->d_J, c->d_H, nullptr); },
+                   /*staged=*/true);
 }
 
 // ---------------------------------------------------------------- host shim: the "new x" protocol
@@ -2456,7 +2395,7 @@ int pk_exchange_sums_dev(pk_ctx* c, const double* d_x, double* d_grad, double* d
   A.xc_box = (unsigned long long* const*)c->xc_box; A.xc_idx = c->xc_idx;
   A.xc_world = c->xc_world; A.xc_rank = c->xc_rank; A.xc_epoch = epoch; A.xc_nsh = c->xc_nsh; A.xc_stride = c->xc_stride;
   A.flags = (A.flags & ~F_WRITE_F) | (write_f ? F_WRITE_F : 0);
-  return launch(c, K_XCHG, A, 1, 0, pick(c, stream));
+  return launch(c, K_XCHG, A, pick(c, stream));
 }
 
 // dst[dst_off + i] = src[src_off + i] over a device table of n_chunks (src_off, dst_off, len) int64 triples
@@ -2466,7 +2405,7 @@ int pk_copy_runs_dev(pk_ctx* c, const int64_t* d_table, int n_chunks, const doub
   if (n_chunks <= 0) return 0;
   PkArgs A = base_args(c, nullptr, nullptr, 0.0);
   A.rc_table = d_table; A.rc_n = n_chunks; A.rc_src = d_src; A.rc_dst = d_dst;
-  return launch(c, K_RUNS, A, (unsigned)(n_chunks < 8192 ? n_chunks : 8192), 0, pick(c, stream));
+  return launch(c, K_RUNS, A, pick(c, stream), n_chunks);
 }
 
 // *d_dst = value, in stream order (d_dst: device address of a 64-bit word, typically of a registered host segment)

@@ -59,7 +59,9 @@ def _intervals_per_wave(plan, override=None, shards=1, subs=0, want_workgroups=F
         for n_p, cap, _ in caps:
             t = math.ceil(max(n_p / shards - 1, 0) / min(ipw, cap)) + 1        # (the first interval is a kind of its own)
             tiles += -(-t // runtime.WAVES_PER_BLOCK) * runtime.WAVES_PER_BLOCK
-        roles = 3 if tiles <= 1024 else 2          # (pk_set_problem: the x-part is split into two roles up to 1024 tiles)
+        # (the grid of pk_cycle in csrc/pk_launch.h: per tile block 3 workgroups while pk_set_problem splits the x-part, up to
+        #  1024 tiles, else 2, or the model's cycle_subs; + 3.  tests/test_cabi.py holds this formula against the table)
+        roles = 3 if tiles <= 1024 else 2
         if subs:
             roles = int(subs)
         per_cu = math.ceil((roles * tiles // runtime.WAVES_PER_BLOCK + 3) / N_CU)
@@ -73,6 +75,36 @@ def _launch_underfills_the_chip(plan, shards=1):
     """True when the one-launch cycle of this mesh, tiled by default, has no more workgroups than the GPU has CUs: the
     cycle's time is then one wave's chain, not throughput (see compile_plan)."""
     return bool(plan.phase_plans) and _intervals_per_wave(plan, shards=shards, want_workgroups=True) <= N_CU
+
+
+def model_desc(src):
+    """The pk_model_desc of a generated model: what the library sizes its launches from (csrc/pk_launch.h)."""
+    plan = src.plan
+    md = runtime.ModelDesc()
+    md.n_phase, md.n_I, md.nred = src.nphase, max(len(plan.I_syms), 1), src.nred
+    md.lds_g, md.lds_j, md.lds_h, md.lds_x = src.lds_g, src.lds_j, src.lds_h, src.lds_x
+    md.ne_j, md.ne_h = src.list_off["jac"]["total"], src.list_off["hess"]["total"]
+    md.ne_a = src.list_off["aux"]["total"]
+    md.ne_hc = src.list_off["hessc"]["total"] if src.compact else 0
+    md.lds_e = src.lds_e
+    md.lds_jc = src.lds_jc
+    md.ne_jc = src.list_off["jacc"]["total"] if src.compact_j else 0
+    md.tab_cap = src.tab_cap
+    md.sharded = int(src.sharded)
+    md.max_phases = src.max_phases
+    md.cycle_subs = src.cycle_subs
+    md.hess_subs = src.h_ngmax if src.cycle_subs else 0
+    # (the stand-alone compact kernels of such a model: a workgroup per pass too)
+    md.hessc_subs = src.hc_ngmax if (src.cycle_subs and src.hc_ngmax > 1) else 0
+    md.jacc_subs = src.jc_ngmax if (src.cycle_subs and src.jc_ngmax > 1) else 0
+    md.big_global, md.big_rows = int(src.big_global), int(src.big_rows)
+    md.wide = int(any(src.wide))      # (the library then refuses pk_xall: _refuse_sequential_values_role)
+    md.prepass_f = 1
+    md.prepass_grad = int(plan.needs_I_grad)
+    md.prepass_g = int(plan.needs_I_con)
+    md.prepass_jac = int(plan.jac.needs_I)
+    md.prepass_hess = int(plan.hess.needs_I)
+    return md
 
 
 def magic_number(d: int) -> int:
@@ -219,7 +251,7 @@ def compile_plan(plan: SystemPlan, sharded=False, output_share=1.0, extra_flags=
     pass evaluates, stages and streams) is searched under two criteria, in this order:
 
     * **LDS** -- every launch of the code object must fit the 160 KiB of a workgroup *including* the table blocks the
-      runtime adds (``ModelSource.launch_lds_bytes``, the bytes ``pk_runtime.cpp::launch_raw`` asks for): the size is halved
+      runtime adds (``ModelSource.launch_lds_bytes``, the bytes of ``csrc/pk_launch.h``): the size is halved
       until it does.  Nothing a wave stages grows with the number of states (WIDE phases, codegen.py), so a fitting size
       exists for every model; if none did, this raises instead of handing the library a model it must reject.
     * **registers** -- a model whose kernels would spill vector registers to scratch memory is generated again with smaller
@@ -398,32 +430,9 @@ class Evaluator:
         self.src, code = compile_plan(plan, sharded=sharded, output_share=output_share, extra_flags=self.hipcc_flags, fixed=_fixed)
         self.ctx = runtime.Context(device)            # raises RuntimeError without a GPU
         lib, h = self.ctx.lib, self.ctx.handle
-        md = runtime.ModelDesc()
-        md.n_phase, md.n_I, md.nred = self.src.nphase, max(len(plan.I_syms), 1), self.src.nred
-        md.lds_g, md.lds_j, md.lds_h, md.lds_x = self.src.lds_g, self.src.lds_j, self.src.lds_h, self.src.lds_x
-        md.ne_j, md.ne_h = self.src.list_off["jac"]["total"], self.src.list_off["hess"]["total"]
-        md.ne_a = self.src.list_off["aux"]["total"]
-        md.ne_hc = self.src.list_off["hessc"]["total"] if self.src.compact else 0
-        md.lds_e = self.src.lds_e
-        md.lds_jc = self.src.lds_jc
-        md.ne_jc = self.src.list_off["jacc"]["total"] if self.src.compact_j else 0
-        md.tab_cap = self.src.tab_cap
-        md.sharded = int(self.src.sharded)
-        md.max_phases = self.src.max_phases
-        md.cycle_subs = self.src.cycle_subs
-        md.hess_subs = self.src.h_ngmax if self.src.cycle_subs else 0
-        # (the stand-alone compact kernels of such a model: a workgroup per pass too)
-        md.hessc_subs = self.src.hc_ngmax if (self.src.cycle_subs and self.src.hc_ngmax > 1) else 0
-        md.jacc_subs = self.src.jc_ngmax if (self.src.cycle_subs and self.src.jc_ngmax > 1) else 0
-        md.big_global, md.big_rows = int(self.src.big_global), int(self.src.big_rows)
-        md.wide = int(any(self.src.wide))      # (the library then refuses pk_xall: _refuse_sequential_values_role)
+        md = model_desc(self.src)
         self._err_views = None
         self._csr = {}
-        md.prepass_f = 1
-        md.prepass_grad = int(plan.needs_I_grad)
-        md.prepass_g = int(plan.needs_I_con)
-        md.prepass_jac = int(plan.jac.needs_I)
-        md.prepass_hess = int(plan.hess.needs_I)
         self._code = code
         self._views = {}
         self.zero_copy = False   # True: callbacks return views of pinned buffers (set by the IPOPT adapter)

@@ -47,7 +47,7 @@ def _stale(target, sources):
 
 def build_runtime(force=False):
     """Compile libpockit_hip.so (host C++ against libamdhip64)."""
-    srcs = [os.path.join(CSRC, "pk_runtime.cpp"), os.path.join(CSRC, "pk_abi.h"),
+    srcs = [os.path.join(CSRC, "pk_runtime.cpp"), os.path.join(CSRC, "pk_abi.h"), os.path.join(CSRC, "pk_launch.h"),
             os.path.join(os.path.dirname(HERE), "include", "pockit_hip.h")]
     if force or _stale(LIB_PATH, srcs):
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O2", "-fPIC", "-shared", "-std=c++17", srcs[0], "-o", LIB_PATH])

@@ -45,11 +45,13 @@ static std::set<FakeStream*> g_streams;
 static std::set<void*> g_host, g_dev;
 static FakeSizes g_sizes;
 static std::vector<std::string> g_log;
+static std::vector<FakeLaunch> g_launches;
 static int g_default_steps = 1;      // queued operations a poll lets run
 
 void fake_hip_set_sizes(const FakeSizes& s) { g_sizes = s; }
 const std::vector<std::string>& fake_hip_log() { return g_log; }
-void fake_hip_clear_log() { g_log.clear(); }
+const std::vector<FakeLaunch>& fake_hip_launches() { return g_launches; }
+void fake_hip_clear_log() { g_log.clear(); g_launches.clear(); }
 size_t fake_hip_live_allocations() { return g_host.size() + g_dev.size(); }
 
 void fake_hip_enqueue(hipStream_t s, std::function<void()> fn) { s->push(std::move(fn)); }
@@ -177,8 +179,8 @@ static void run_kernel(const std::string& name, const std::vector<char>& argbuf)
   }
 }
 
-hipError_t hipModuleLaunchKernel(hipFunction_t f, unsigned gx, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, hipStream_t s,
-                                 void**, void** extra) {
+hipError_t hipModuleLaunchKernel(hipFunction_t f, unsigned gx, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned shmem,
+                                 hipStream_t s, void**, void** extra) {
   std::vector<char> buf;
   if (extra && extra[0] == HIP_LAUNCH_PARAM_BUFFER_POINTER && extra[2] == HIP_LAUNCH_PARAM_BUFFER_SIZE) {
     const size_t sz = *static_cast<size_t*>(extra[3]);
@@ -186,7 +188,7 @@ hipError_t hipModuleLaunchKernel(hipFunction_t f, unsigned gx, unsigned, unsigne
   }
   const std::string name = f->name;
   g_log.push_back(name);
-  (void)gx;
+  g_launches.push_back(FakeLaunch{name, gx, shmem, buf.size()});
   s->push([name, buf]() { run_kernel(name, buf); });
   return hipSuccess;
 }

@@ -14,6 +14,14 @@ struct FakeSizes {
 void fake_hip_set_sizes(const FakeSizes& s);
 const std::vector<std::string>& fake_hip_log();
 void fake_hip_clear_log();
+// every kernel launch as the runtime shaped it, in launch order (beside the string log above, which also holds the copies)
+struct FakeLaunch {
+  std::string kernel;
+  unsigned grid = 0;            // workgroups
+  size_t lds_bytes = 0;         // dynamic LDS per workgroup
+  size_t arg_bytes = 0;         // kernel-argument segment
+};
+const std::vector<FakeLaunch>& fake_hip_launches();
 size_t fake_hip_live_allocations();
 double fake_f(const double* x, int n);
 double fake_grad(const double* x, int n, int64_t i);

@@ -13,19 +13,44 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = os.path.join(ROOT, "tests", "fake_hip")
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
-def test_host_runtime_under_address_and_undefined_behaviour_sanitizers(tmp_path):
-    exe = str(tmp_path / "pk_runtime_sanitized")
+SANITIZER_ENV = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+
+
+@pytest.fixture(scope="module")
+def driver_exe(tmp_path_factory):
+    """tests/fake_hip/driver.cpp + the runtime + the stand-in, built once with the address and undefined-behaviour sanitizers."""
+    exe = str(tmp_path_factory.mktemp("runtime") / "pk_runtime_sanitized")
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
            "-fno-sanitize-recover=undefined", "-I", FAKE, "-I", ROOT,
            os.path.join(ROOT, "pockit_amd", "csrc", "pk_runtime.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
            os.path.join(FAKE, "driver.cpp"), "-o", exe]
     build = subprocess.run(cmd, capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
+    return exe
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_host_runtime_under_address_and_undefined_behaviour_sanitizers(driver_exe):
+    env = dict(os.environ, **SANITIZER_ENV)
+    run = subprocess.run([driver_exe], capture_output=True, text=True, env=env, timeout=600)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])
     assert "checks passed" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_launch_shapes_are_those_of_the_recorded_trace(driver_exe):
+    """Grid, dynamic LDS bytes and kernel-argument bytes of every launch, and the order of copies and kernels of every entry
+    point, over the driver's scenarios and over descriptors that reach every row of csrc/pk_launch.h: byte for byte what
+    tests/fake_hip/launch_trace.txt recorded from the runtime BEFORE the launch shapes moved into that table (its first
+    line names the commit).  The file is a recording of that commit, never regenerated from the code under test."""
+    with open(os.path.join(FAKE, "launch_trace.txt")) as fh:
+        head, recorded = fh.read().split("\n", 1)
+    assert head.startswith("# ")
+    env = dict(os.environ, **SANITIZER_ENV)
+    run = subprocess.run([driver_exe, "--launch-trace"], capture_output=True, text=True, env=env, timeout=600)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])
+    assert "ERROR" not in run.stderr and "runtime error" not in run.stderr
+    assert run.stdout == recorded
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
