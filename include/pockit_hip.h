@@ -1,5 +1,11 @@
 /* pockit_hip.h -- C ABI of the MI355X NLP-callback evaluator (libpockit_hip.so).
  *
+ * STABLE SURFACE.  The 35 entry points declared here are the contract of the library: what a second host binding for
+ * pockit's evaluator path needs -- life cycle, evaluation on host buffers and on device pointers, the compact layouts, the CSR
+ * hand-off and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
+ * shim, the sharding transport, the helper threads, tuning switches and diagnostics) is declared in
+ * pockit_amd/csrc/pockit_hip_internal.h and may change with the project.
+ *
  * Drop-in boundary: these entry points are what a host binding for pockit's evaluator path
  * binds.  Each eval function replaces one method of the reference's cyipopt ``problem_obj``
  * (class SystemBase in /root/reference/pockit/base/systembase.py):
@@ -138,96 +144,6 @@ int pk_eval_hess(pk_ctx* ctx, const double* x, const double* lambda, double sigm
 int pk_eval_cycle(pk_ctx* ctx, const double* x, const double* lambda, double sigma, double* f, double* grad,
                   double* g, double* jac, double* hess);
 
-/* "new x" protocol for host shims.  cyipopt calls objective / gradient / constraints / jacobian separately but on the
- * same iterate, then hessian with fresh multipliers (the five methods ipopt.py:41-53 hands over as ``problem_obj``).
- *   pk_same_x      1 if ``x`` equals the x of the last pk_prepare_x bit for bit (its results are still held)
- *   pk_prepare_x   stages x in pinned memory, uploads it, runs the fused x-kernel (every node evaluated once for f,
- *                  grad f, g, J) and queues the copies of the results into pinned host memory right behind it, in the
- *                  order a solver asks for them -- nothing waits; x and lambda staging is double-buffered
- *   pk_fetch       waits for ONE result (what: 0 f, 1 grad[n], 2 g[m], 3 jac[nnz_J]); out == NULL leaves it where it
- *                  landed (pk_result_location), otherwise it is copied on to ``out``
- *   pk_eval_hess_prepared   Hessian of the Lagrangian on the prepared x (x is not uploaded again)
- *   pk_set_result_targets   where the results of the NEXT prepare / Hessian land: pinned memory of the caller
- *                  (pk_host_alloc; a solver-side array that outlives the call), NULL = the context's own buffers
- *   pk_set_host_mode        prefetch 1 (default): all four x-results are copied out behind the kernel; 0: f and g
- *                  always, grad f and J on first request (a line search's rejected trial points never ask);
- *                  host_direct 1: the kernels store into the pinned host targets themselves (no DMA; A/B switch)
- *   pk_invalidate_x         forget the prepared x (the context's buffers were used by another entry point) */
-/* the compact Hessian layout (pk_eval_hessc: one value per distinct position of a node) on the x of the last pk_prepare_x,
- * multipliers given or staged by pk_stage_lambda; vals_pinned = 1: `vals` is pk_host_alloc memory the DMA writes directly.
- * What SystemBase.hessian (systembase.py:820-835) becomes for a solver that was handed the compact structure. */
-int pk_eval_hessc_prepared(pk_ctx* ctx, const double* lambda, double sigma, double* vals, int vals_pinned);
-int pk_same_x(pk_ctx* ctx, const double* x);
-int pk_same_bits(const double* a, const double* b, size_t n);   /* 1 if equal bit for bit (memcmp), for host shims */
-int pk_copy_bits(double* dst, const double* src, size_t n);      /* dst = src (non-overlapping), for host shims */
-/* k helper threads (0 = none, the default; <= 16) that take slices of pk_same_bits / pk_copy_bits passes of 256 KB and more:
- * rank 0 of the host-landed sharded cycle stages and compares an x that is N times as long as one GPU's.
- * Process-wide; helpers spin for 1 ms after the last pass, otherwise they sleep in 20 us steps. */
-int pk_host_threads(int k);
-long pk_host_threads_jobs(void); /* slices of passes the helpers have executed so far (diagnostics) */
-int pk_host_threads_hot(void);   /* how many of them are spinning right now (diagnostics); -1: the pool gave up -- the caller waited
-                                  * more than 1 ms for a helper three times (a host whose CPUs are time slices of fewer cores) */
-int pk_prepare_x(pk_ctx* ctx, const double* x);
-int pk_fetch(pk_ctx* ctx, int what, double* out);
-int pk_eval_hess_prepared(pk_ctx* ctx, const double* lambda /* NULL: staged */, double sigma, double* vals);
-/* queue the upload of the next Hessian's multipliers and return (the x check then overlaps the DMA) */
-int pk_stage_lambda(pk_ctx* ctx, const double* lambda);
-int pk_set_result_targets(pk_ctx* ctx, double* f, double* grad, double* g, double* jac, double* hess);
-/* ONE call per callback of a host shim (what a cyipopt binding makes of the five methods it is handed, ipopt.py:41-53):
- *   pk_callback_x     what = 0 objective (systembase.py:602), 1 gradient (:646), 2 constraints (:613), 3 jacobian (:676).
- *                     If `x` is not the prepared iterate it becomes it (pk_prepare_x) and *fresh = 1; its results then land
- *                     in `block`, pinned memory of the caller's laid out like the library's own buffers,
- *                     [J (nnz_J) | grad f (n) | g (m)] (NULL: the context's buffers, pk_host_buffer) -- the pieces of J that
- *                     change with x, grad f and g leave the device in ONE copy.  Then result `what` is waited for; f_out
- *                     receives f for what = 0.  A block must stay allocated until every result of its iterate has been
- *                     fetched or the context's stream has been synchronized (pk_sync, pk_destroy): all results of a new x
- *                     are on their way into it whether or not they are asked for.
- *   pk_callback_hess  SystemBase.hessian (systembase.py:820-835): stages the multipliers, prepares a new x as above, evaluates
- *                     the Hessian of the Lagrangian into `hess` (pinned memory of the caller's or NULL = the context's
- *                     buffer; compact = 1: the compact layout of pk_eval_hessc, `hess` required) and waits for it.
- *   pk_set_jac_constant_runs   runs [start, stop) of the Jacobian values that do not depend on x (the +-1 translation entries
- *                     of phasebase.py:1071-1081 and constant boundary items: 19 % of J at 12k quadrotor nodes): the copy to the
- *                     host skips them from then on; every landing array must have been filled once with
- *   pk_fill_jac_constants      (the context's own buffer is filled by pk_set_jac_constant_runs itself).
- *   pk_set_host_option         A/B switches (default): "spin_wait" (1), "lambda_direct" (1), "chunk_upload" (1), "kernel_upload"
- *                              "separate_x" (0; 1: the five callbacks and the cycle through the stand-alone kernels one after the other,
- *                              never the fused kernel -- the fallback of a code object whose fused kernel fails its self-check),
- *                     (1), "kernel_download" (8: up to that many MiB per copy), "split_copy" (1), "speculative_hess" (1), "mark_wait" (1: the callbacks wait on a word a one-thread
- *                     kernel stores behind the result copies instead of on the stream's state), "hess_direct"
- *                     (1: a Hessian of at most "kernel_download" MiB is stored into its pinned landing array by the kernel itself),
- *                     "xpart_single" (1: the x-results of a new iterate come from ONE launch, pk_cycle without its Hessian role),
- *                     "adaptive_prefetch" (1: grad f and J of a new iterate are copied ahead only
- *                     if they were asked for at the previous one -- a line search's rejected trial points ask for f and g only),
- *                     "small_x_kb" (128: the x threshold of small_direct in KB, an A/B knob),
- *                     "small_direct" (1: an x of <= 128 KB is read by the kernels from its pinned staging buffer, x-results of
- *                     <= 1 MB are stored by the kernel straight into the landing block: no upload / copy launches)
- *                     -- see pk_runtime.cpp. */
-int pk_callback_x(pk_ctx* ctx, int what, const double* x, double* block, double* f_out, int* fresh);
-int pk_callback_hess(pk_ctx* ctx, const double* x, const double* lambda, double sigma, double* block, double* hess,
-                     int compact, int* fresh);
-/* all five results of one iterate in ONE call and ONE launch, for a caller that has the multipliers together with x
- * (Evaluator.cycle; SystemBase's five callbacks evaluated at once): same staging and landing as the two callbacks above --
- * `block` = [J | grad f | g] pinned with its constant entries filled in, `hess` = nnz_H pinned values -- returns when
- * everything has landed; the iterate is then the prepared one (pk_callback_x on the same x is served from the block). */
-int pk_callback_cycle(pk_ctx* ctx, const double* x, const double* lambda, double sigma, double* block, double* hess,
-                      double* f_out);
-int pk_set_jac_constant_runs(pk_ctx* ctx, int n_runs, const int64_t* start, const int64_t* stop);
-int pk_fill_jac_constants(pk_ctx* ctx, double* jac /* nnz_J */);
-int pk_set_host_option(pk_ctx* ctx, const char* name, int value);
-/* layout of the Jacobian the host shim serves (pk_fetch(3), pk_callback_x(3), the J part of a landing block): 0 the reference's
- * triplets (default), 1 the compact layout of pk_eval_jacc (a landing block is then [J compact (nnz_Jc) | grad f | g]) */
-int pk_set_jacobian_layout(pk_ctx* ctx, int compact);
-int pk_result_location(pk_ctx* ctx, int what /* 0..4 */, double** ptr);
-int pk_set_host_mode(pk_ctx* ctx, int prefetch, int host_direct);
-int pk_invalidate_x(pk_ctx* ctx);
-/* Pinned (page-locked) result buffers owned by the context: what = 0 f, 1 grad, 2 g, 3 jac, 4 hess.  The default
- * landing place of the results; reused by the next iterate. */
-int pk_host_buffer(pk_ctx* ctx, int what, double** ptr, int64_t* count);
-/* Pinned, device-visible host memory that is NOT tied to a context (result arrays handed to a solver may outlive the
- * evaluator): DMA targets at full PCIe rate.  pk_last_error(NULL) holds the message of a failure. */
-int pk_host_alloc(size_t bytes, void** out);
-int pk_host_free(void* p);
-
 /* Compact Hessian of the Lagrangian: the reference repeats every dynamics entry for
  * each nonzero of the integration matrix (phasebase.py:923-928,1280-1285; 10-20x duplication); here lambda is
  * contracted first (mu = I^T lambda) and entries of a node with equal (row, col) are summed, so one value per
@@ -294,90 +210,12 @@ int pk_eval_xpart_dev(pk_ctx* ctx, const double* d_x, double* d_f, double* d_gra
  * per context at a time (the launch owns the context's hand-off slots). */
 int pk_eval_cycle_dev(pk_ctx* ctx, const double* d_x, const double* d_lambda, double sigma, double* d_f,
                       double* d_grad, double* d_g, double* d_jac, double* d_hess, void* stream);
-/* `count` back-to-back cycles on the same buffers, enqueued by the library (a solver written against the C ABI launches from
- * compiled code; bench.py's timed batches go through this so that no interpreter loop paces the stream).  xchg = 1: every
- * cycle is followed by pk_exchange_sums_dev(d_x, d_xgrad, d_f) -- the two-launch form of a sharded cycle.  No reference
- * counterpart (the reference's callbacks are synchronous NumPy calls, systembase.py:602-835). */
-int pk_eval_cycle_dev_repeat(pk_ctx* ctx, const double* d_x, const double* d_lambda, double sigma, double* d_f, double* d_grad,
-                             double* d_g, double* d_jac, double* d_hess, void* stream, int count, int xchg, double* d_xgrad);
-/* Replay the fused cycle from a cached hipGraph while its pointers, sigma and stream do not change (a solver's
- * steady state); any change re-captures.  Off by default. */
-int pk_set_cycle_graph(pk_ctx* ctx, int enable);
-/* single_launch = 1 (default): pk_cycle; 0: the two-launch form, pk_xall then pk_hess, which also reduces */
-int pk_set_cycle_mode(pk_ctx* ctx, int single_launch);
 /* Which layouts pk_eval_cycle_dev[_repeat] writes: 0 = the reference's triplet lists (systembase.py:676-693, 820-835), 1 = the
  * compact layouts of pk_set_problem (nnz_Jc / nnz_Hc values: pk_eval_jacc / pk_eval_hessc).  A compact
  * cycle stays ONE launch: the compact kernels' tile code runs in the Jacobian / Hessian roles of pk_cycle.  Error 69 for a
  * model whose system functions are nonlinear in the integrals or a mesh with an interval of more than 64 points. */
 int pk_set_cycle_layout(pk_ctx* ctx, int jac_compact, int hess_compact);
 int pk_sync(pk_ctx* ctx, void* stream);
-int pk_wait_idle(pk_ctx* ctx, void* stream);   /* the same by polling the stream (returns a few microseconds earlier) */
-
-/* Mesh-interval sharding across GPUs (one context per GPU, each holding its shard of the tiles):
- * ``secondary`` shards skip the boundary-node / system-level work (done once, on the primary);
- * with ``external_prepass`` the callbacks do not run the integral pre-pass themselves: the caller
- * runs pk_eval_integrals_dev, sums ``d_integrals`` (n_I doubles, caller-owned) across shards
- * (RCCL all-reduce) and only then calls the callbacks / pk_eval_f_from_integrals_dev. */
-int pk_set_shard(pk_ctx* ctx, int secondary, int external_prepass, double* d_integrals);
-int pk_eval_integrals_dev(pk_ctx* ctx, const double* d_x, void* stream);
-/* models nonlinear in the integrals (outer-product Hessian blocks, easyderiv.py:323-459) as shards: pk_eval_hess_dev leaves
- * the quadrature-weighted gradient entries of the integrals of THIS shard's nodes in the auxiliary buffer (pk_aux_buffer;
- * entries of other shards' nodes stay zero); the caller sums the buffers over the ranks into a buffer of its own and the
- * primary rank forms the blocks from the sum with pk_eval_outer_dev (into the Hessian values, reference positions). */
-int pk_aux_buffer(pk_ctx* ctx, double** d_ptr, int64_t* count);
-int pk_eval_outer_dev(pk_ctx* ctx, const double* d_aux_sum, double* d_vals /* nnz_H */, void* stream);
-int pk_eval_f_from_integrals_dev(pk_ctx* ctx, const double* d_x, double* d_f, void* stream);
-
-/* Sharded cycles without a collective in the data path.  Every rank leaves its shard's slices of grad f / g / J / H in
- * its own HBM (pk_eval_cycle_dev on its tiles); what couples the shards is the handful of sums over all nodes -- the
- * integrals (-> f) and the gradient entries of t0 / tf / static parameters.  pk_exchange_sums_dev posts this rank's
- * partial vector into every peer's mailbox (peer-mapped fine-grained device memory: pk_device_alloc + pk_ipc_export on
- * the owner, pk_ipc_open on the peers), waits for theirs and adds them in rank order inside ONE one-workgroup launch.
- * pk_set_shared_grad_target redirects a shard's partial sums of the shared gradient slots (used when its gradient
- * output points at another GPU's buffer: the reassembly of the triplets on one GPU by direct peer stores).
- * pk_copy_runs_dev is the pack / unpack pass of the RCCL gather / all-gather forms of the reassembly (A/B). */
-int pk_device_alloc(pk_ctx* ctx, size_t bytes, int finegrained, void** out);
-int pk_device_free(pk_ctx* ctx, void* p);
-int pk_ipc_export(pk_ctx* ctx, void* dptr, void* handle64 /* 64 bytes out */);
-int pk_ipc_open(pk_ctx* ctx, const void* handle64, void** out);
-int pk_ipc_close(pk_ctx* ctx, void* p);
-int pk_set_shared_grad_target(pk_ctx* ctx, double* d_grad_shared);
-/* Host-landed sharded cycle (every GPU lands its slices in ONE host array over its own PCIe link): a host
- * region several processes map (shared memory) is page-locked and made device-visible in every process
- * (pk_host_register), the ranks' run-copy kernels (pk_copy_runs_dev) store their owned runs straight into it;
- * pk_copy_dev is an asynchronous copy between any two device-visible addresses. */
-int pk_host_register(pk_ctx* ctx, void* p, size_t bytes, void** dev_ptr);
-int pk_host_unregister(pk_ctx* ctx, void* p);
-int pk_copy_dev(pk_ctx* ctx, void* dst, const void* src, size_t bytes, void* stream);
-int pk_set_exchange(pk_ctx* ctx, int world, int rank, const void* d_boxes, const int32_t* d_idx, int n_sh, int stride);
-/* pk_set_exchange: every rank's mailbox holds 2 * world * stride words + 16 state words (zeroed here on this rank: the caller
- * puts a barrier between the set-up and the first cycle).  pk_exchange_status: cycles exchanged so far and how many of them
- * timed out waiting for a peer (then this rank's sums read NaN). */
-int pk_exchange_status(pk_ctx* ctx, void* stream, int64_t* cycles, int64_t* timed_out);
-int pk_exchange_sums_dev(pk_ctx* ctx, const double* d_x, double* d_grad, double* d_f, int epoch /* <= 0: counted on the device */,
-                         int write_f, void* stream);
-/* 1: the finalize workgroup of pk_eval_cycle_dev's launch exchanges the partial sums itself -- a sharded cycle is ONE
- * launch per GPU; 0 (default): pk_exchange_sums_dev is a launch of its own behind it. */
-int pk_set_exchange_inline(pk_ctx* ctx, int enable);
-int pk_copy_runs_dev(pk_ctx* ctx, const int64_t* d_table, int n_chunks, const double* d_src, double* d_dst, void* stream);
-/* a progress mark: *d_dst = value once everything enqueued before it on the stream has finished (d_dst: device address of an
- * 8-byte aligned word, e.g. inside a segment registered with pk_host_register -- the host-landed sharded cycle lets rank 0
- * poll such words instead of waiting for the other processes to notice that their GPU has finished) */
-int pk_store_word_dev(pk_ctx* ctx, void* d_dst, int64_t value, void* stream);
-
-/* HIP-event timing of the individual kernels on the launch stream.
- * kernel ids: 0 pk_int, 1 pk_fin, 2 pk_g, 3 pk_grad, 4 pk_jac, 5 pk_hess, 6 pk_xall, 7 pk_aux, 8 pk_outer,
- * 9 pk_hessc, 10 pk_err, 11 pk_csr, 12 pk_cycle, 13 pk_xchg, 14 pk_runs, 15 pk_jacc.  pk_profile_sampling(n): only every n-th launch of a selected kernel is timed (a timed
- * launch costs ~2-3 us more than a plain one, so timing every launch slows the loop being measured). */
-int pk_profile(pk_ctx* ctx, int kernel_mask /* bit k: time kernel k; 0 = off */);
-int pk_profile_sampling(pk_ctx* ctx, int period);
-/* Developer tracing: with a model generated under POCKIT_AMD_TRACE=1 the waves of pk_cycle / pk_xall store the
- * constant-rate device clock (s_memrealtime) at up to 16 checkpoints of their record.  The first call arms the
- * buffer; later calls copy the [3 n_tiles + 3][16] marks out (records: [tile][values, Jacobian, Hessian wave], then
- * pk_cycle's boundary-J, boundary-H and finalize workgroups) and clear the buffer. */
-int pk_trace_read(pk_ctx* ctx, uint64_t* out, int64_t count);
-int pk_profile_read(pk_ctx* ctx, int kernel_id, int64_t* launches, double* total_ms);
-const char* pk_kernel_name(int kernel_id);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,343 @@
+// pk_runtime.h -- private to the translation units of the host runtime (libpockit_hip.so):
+//
+//   pk_runtime.cpp  core: context, model, problem, the launch machinery, device-pointer and one-shot host evaluation, cycle
+//   pk_shim.cpp     host shim: prepared-x protocol, landing blocks, copy batching, polling waits, its A/B options
+//   pk_pool.cpp     helper threads of the host's passes over x and lambda (no HIP, no pk_ctx: includes pk_error.h only)
+//   pk_shard.cpp    sharding: shard flags, peer / IPC / registered memory, the exchange of the partial sums, run copies
+//   pk_extras.cpp   CSR hand-off, mesh error estimation, profiling and developer tracing
+//   pk_error.cpp    fail(): where an error message is kept
+//
+// Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
+// few helpers that cross a unit boundary.  The helpers of the per-callback path are either defined in
+// pk_shim.cpp, beside the callbacks, or inline here.
+#ifndef PK_RUNTIME_H
+#define PK_RUNTIME_H
+
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/pockit_hip.h"
+#include "pockit_hip_internal.h"
+#include "pk_error.h"
+#define PK_MAX_PHASES 128     // (= PK_HOST_MAX_PHASES: the host-side PkArgs holds the most a code object may ask for)
+#include "pk_abi.h"
+#include "pk_launch.h"        // kernel ids and names; grid and LDS bytes of every launch
+
+enum { F_WRITE_F = 1, F_SECONDARY = 2, F_FIN_INT = 8, F_FIN_GRAD = 16, F_SPLIT = 32, F_XCHG = 64, F_NO_HESS = 128,
+       F_COMPACT_H = 256, F_COMPACT_J = 512 };
+
+struct EventPair {
+  hipEvent_t a, b;
+};
+
+// ---- sharding (pk_shard.cpp): pk_set_shard, pk_set_shared_grad_target
+struct PkShard {
+  int flags = 0;                 // OR-ed into PkArgs.flags (bit 1: secondary shard)
+  bool external_prepass = false; // sharded mode: the caller all-reduces the integrals itself
+  double* ext_I = nullptr;       // caller-owned integral buffer (sharded mode)
+  double* gshared = nullptr;     // pk_set_shared_grad_target: where the shared gradient slots go (NULL: the gradient itself)
+};
+
+// ---- pk_set_exchange (pk_shard.cpp): peer-mapped mailboxes of the partial-sum exchange (pk_xchg)
+struct PkExchange {
+  const unsigned long long* const* box = nullptr;
+  const int32_t* idx = nullptr;
+  int32_t world = 0, rank = 0, nsh = 0, stride = 0;
+  unsigned long long* own = nullptr;   // this rank's own mailbox (host copy of the pointer: state block, pk_exchange_status)
+  bool in_launch = false;       // pk_cycle's finalize workgroup exchanges the partial sums itself (pk_set_exchange_inline)
+};
+
+// ---- cached hipGraph of the fused callback cycle (pk_set_cycle_graph; pk_runtime.cpp: drop_cycle_graph)
+struct PkCycleKey {
+  const void *x, *lam, *f, *grad, *g, *jac, *hess;
+  double sigma;
+  hipStream_t st;
+  bool operator==(const PkCycleKey& o) const {
+    return x == o.x && lam == o.lam && f == o.f && grad == o.grad && g == o.g && jac == o.jac && hess == o.hess &&
+           sigma == o.sigma && st == o.st;
+  }
+};
+struct PkGraph {
+  bool use = false;
+  hipGraphExec_t cyc_exec = nullptr;
+  hipGraphExec_t rep_exec = nullptr;      // pk_eval_cycle_dev_repeat: a batch of rep_count cycles as one graph
+  int rep_count = 0;
+  PkCycleKey cyc_key{}, rep_key{};
+};
+
+// ---- profiling and developer tracing (pk_extras.cpp: free_trace; the timed launch itself is launch_raw's)
+struct PkProfile {
+  bool on = false;
+  unsigned mask = 0;
+  unsigned period = 1;          // time every n-th launch of a selected kernel
+  unsigned seen[K_COUNT] = {};
+  std::vector<EventPair> pending[K_COUNT];
+  std::vector<EventPair> free_events;
+  int64_t launches[K_COUNT] = {};
+  double total_ms[K_COUNT] = {};
+  unsigned long long* d_trace = nullptr;   // developer tracing buffer, [n_tiles][16]
+};
+
+// ---- triplet -> CSR map (pk_set_csr_map; pk_extras.cpp: free_csr)
+struct PkCsrMap {
+  int32_t *d_seg = nullptr, *d_perm = nullptr;
+  double* d_vals = nullptr;
+  int64_t n_unique = 0, n_triplets = 0;
+};
+
+// ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
+struct PkMeshError {
+  void* d_iv = nullptr;
+  int32_t* d_grp = nullptr;     // (first record, count) per wavefront of pk_err
+  double *d_db = nullptr, *d_T = nullptr, *d_I = nullptr;
+  int32_t n_groups = 0;
+  int64_t n_out = 0;
+  double* d_stage = nullptr;    // staging rows of intervals with more than 264 augmented nodes
+  int32_t row = 0, slot = 0;
+};
+
+// ---- host shim (pk_shim.cpp: alloc_shim, free_shim)
+// one result of the current iterate: 0 f, 1 grad f, 2 g, 3 J, 4 H
+struct PkResult {
+  double* h_out = nullptr;       // the context's own pinned landing place
+  double* target = nullptr;      // pk_set_result_targets (NULL: h_out)
+  bool target_visible = true;    // the device can store into target itself
+  bool target_pinned = false;    // target is pinned memory by contract (landing blocks)
+  double* landed = nullptr;      // where the result of the current iterate went
+  hipEvent_t ev_out = nullptr;
+  bool enq = false;              // copy of the result is enqueued
+  bool done = false;             // ... and known to have landed
+  bool stored_direct = false;    // the kernel stored the result into its landing place
+  int ev_of = 0;                 // the event that covers the result (one event per batch of copies); default: its own, see PkShim()
+};
+
+struct PkShim {
+  PkShim() { for (int k = 0; k < 5; ++k) res[k].ev_of = k; }
+  double* h_Hc = nullptr;      // pinned landing place of the compact Hessian (pk_eval_hessc_prepared), allocated on first use
+  // pinned host staging: x and lambda are double-buffered (the upload of iterate k + 1 does not wait for anything of
+  // iterate k), results land in res[k].h_out (f, grad, g, J, H) or in caller-supplied pinned targets
+  double *h_xs[2] = {nullptr, nullptr}, *h_lams[2] = {nullptr, nullptr};
+  hipEvent_t ev_xs[2] = {nullptr, nullptr}, ev_lams[2] = {nullptr, nullptr};   // upload k of the buffer has left it
+  int xbuf = 0, lambuf = 0;
+  double* h_x = nullptr;                   // the staging buffer holding the x of the last pk_prepare_x (pk_same_x)
+  bool x_valid = false;
+  bool lam_staged = false;                 // pk_stage_lambda ran, pk_eval_hess_prepared has not consumed it yet
+  PkResult res[5];
+  unsigned long long status_seen[2] = {0, 0};   // PkArgs.status as of the last check (handoff_check)
+  int poll_limit = 0;                           // > 0: poll rounds before a hand-off gives up ("poll_limit" host option; tests)
+  int prefetch = 1;            // 1: every x-only result is copied out right behind the kernel; 0: on first request
+  int adaptive_prefetch = 1;   // ... but grad f and J only while the solver keeps asking for them: an iterate whose Jacobian was
+                               // never asked for was a rejected trial point of a line search (f and g only), and the copy of
+                               // its J (122 us of link time at 12k nodes) stood in the way of the next trial point's upload;
+                               // the new x behind such an iterate gets grad f / J on request
+  bool cur_J_asked = true;     // grad f or J of the prepared iterate has been asked for
+  int host_direct = 0;         // 1: the kernels store into the (pinned, device-visible) host targets themselves
+  // Host-shim tuning (pk_set_host_option; defaults = what measured fastest on MI355X, tools/dma_probe.cpp):
+  int spin_wait = 1;           // results are awaited by polling (the event's state / f's own pinned word), not hipEventSynchronize
+  int lambda_direct = 1;       // the Hessian kernel of the prepared protocol reads the multipliers from the pinned staging
+                               // buffer itself (one pass over PCIe inside the kernel) instead of an upload in front of it;
+                               // applied up to 2 MB of multipliers (12k nodes: -8 us; at 3.2 MB the chunk-pipelined upload
+                               // wins by 16 us: the staging memcpy then overlaps the link)
+  int chunk_upload = 1;        // staging of large inputs is pipelined with their upload in a few chunks
+  int kernel_upload = 1;       // x (and lambda) go up through a copy kernel on the compute queue instead of the DMA engine: the
+                               // kernel behind it then starts without a cross-engine hand-off (~10 us on the path to f)
+  int kernel_download = 8;     // results of up to this many MiB per piece come down through a copy kernel instead of the DMA
+                               // engine (0: never): no cross-engine hand-off behind the kernel that produced them (~10 us per
+                               // copy), but 51 instead of 56 GB/s on the link -- the DMA engine wins from ~5 MB on
+  int split_copy = 1;          // grad f | g leave in a copy of their own in front of J (+1 DMA), with an event behind it: the
+                               // gradient and constraints callbacks return while J is still on the link, and the bitwise
+                               // compares of x they and the Jacobian callback start with are hidden behind that copy
+  int small_direct = 1;        // small systems are bound by the number of launches, not by bytes: a kernel reads an x of at most
+                               // 128 KB from its pinned staging buffer (no upload launch) and stores x-results of at most 1 MB
+                               // straight into their pinned landing places (no copy launches) -- LQR 10x10: 53 -> us per iterate
+  int small_x_kb = 128;            // (the x threshold of small_direct, in KB: an A/B knob)
+  const double* x_src = nullptr;   // where the kernels read the prepared x: d_x, or (small_direct) the pinned staging buffer
+  int hess_direct = 1;         // the Hessian kernel stores into the pinned landing place itself when H is small enough for the
+                               // copy kernel (kernel_download): no launch behind it, its reads of lambda and its stores share
+                               // the link in both directions (12k nodes: 97 -> 93 us; at 83 MB the copy is faster)
+  int speculative_hess = 1;    // pk_callback_hess launches on the prepared x BEFORE comparing x with it (the compare then runs
+                               // while the GPU works; a different x -- rare -- discards the launch and starts over)
+  // reuse guard of the staging buffers without events: every enqueue takes a sequence number; an idle stream seen by the host
+  // (wait_result) retires all numbers issued so far
+  uint64_t op_seq = 0, idle_seq = 0;
+  // mark_wait: behind the last result copy of a batch a one-word kernel stores a counter into pinned memory (res[0].h_out[4])
+  // and the waiting callback polls that word instead of the stream's state (the runtime's query answers several microseconds
+  // after the word is there; the stream is still asked now and then, so a failed launch does not hang the caller)
+  int mark_wait = 1;
+  unsigned long long mark_val = 0;     // value of the last mark enqueued
+  uint64_t mark_op_seq = 0;            // op_seq when it was enqueued: everything up to it has finished once the mark is seen
+  bool mark_pending = false;           // the last thing enqueued for the results is a mark nobody has waited for yet
+  uint64_t xs_seq[2] = {0, 0}, lams_seq[2] = {0, 0};
+  hipEvent_t ev_early = nullptr;     // behind the grad f | g copy of the current iterate (split_copy)
+  bool early_valid = false;
+  const double* lam_src = nullptr;   // where the staged multipliers are read from (d_lam, or the pinned staging buffer)
+  // Pieces [start, stop) of the Jacobian values that CHANGE with x.  Default: everything.  pk_set_jac_constant_runs takes
+  // x-independent runs (the +-1 translation entries of phasebase.py:1071-1081 are 19 % of J at 12k nodes) out of the
+  // per-iterate copy: they are put into a landing array once (pk_fill_jac_constants) and never cross PCIe again.
+  std::vector<std::pair<int64_t, int64_t>> jruns, jconst;      // (of the layout the shim serves; the other layout's are parked)
+  std::vector<std::pair<int64_t, int64_t>> jruns_other, jconst_other;
+  bool jac_compact = false;    // the host shim's Jacobian callback serves the compact layout (pk_set_jacobian_layout)
+  bool target_filled = false;  // the caller's J landing array (res[3].target) already holds the constant runs (pk_callback_x blocks)
+  bool jac_filled = false;     // ... and so does the landing place of the CURRENT iterate: its copy skips them
+};
+
+struct pk_ctx : pk_error_state {
+  // ---- core (pk_runtime.cpp: free_problem)
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipModule_t module = nullptr;
+  hipFunction_t fn[K_COUNT] = {};
+  bool have_model = false, have_problem = false;
+  bool split_xall = false;      // pk_xall with two waves per tile (values / Jacobian), see pk_set_problem
+  int cycle_mode = 1;           // 1: single-launch pk_cycle; 0: pk_xall + pk_hess (pk_set_cycle_mode)
+  int cycle_layout = 0;         // what pk_eval_cycle_dev writes: bit 0 compact Jacobian, bit 1 compact Hessian (pk_set_cycle_layout)
+  // (two switches of pk_set_host_option that choose among the core's launches)
+  int xpart_single = 1;        // pk_eval_xpart_dev as ONE launch (pk_cycle without its Hessian role) instead of pk_xall + pk_fin
+  bool separate_x = false;     // the five callbacks one after the other through the STAND-ALONE kernels (pk_int + pk_fin, pk_grad, pk_g,
+                               // pk_jac, pk_hess), as for a model that needs the integrals first: what pockit_amd.Evaluator.checked falls back
+                               // to when a code object's fused kernel fails its self-check (round 5)
+  bool has_big = false;         // the mesh has intervals with more than 64 points (one workgroup each, PK_BIG code objects)
+  // staging rows of intervals with more than 256 points (they do not fit the workgroup's LDS rows): slots in device memory
+  double* d_big_stage = nullptr;
+  int32_t big_row = 0, big_slot = 0;
+  unsigned long long *d_cpart = nullptr, *d_cpart2 = nullptr;   // pk_cycle's hand-off slots (PK_EMPTY between launches)
+  size_t cpart_slots = 0;
+  int debug_flags = 0;          // diagnostic kernel switches (POCKIT_AMD_DEBUG_FLAGS), never set in production
+  pk_model_desc md{};
+  // problem
+  int32_t n = 0, m = 0, n_sys = 0, n_s = 0, l_s = 0, n_phase = 0, n_tiles = 0;
+  int64_t nnz_J = 0, nnz_H = 0;
+  int32_t n_items_jac = 0, n_items_hess = 0, n_items_aux = 0, n_outer = 0, n_aux = 0, gz_off = 0, n_gz = 0;
+  int32_t n_items_hessc = 0, n_items_jacc = 0;
+  int64_t nnz_Hc = 0, nnz_Jc = 0;
+  void* d_items_jacc = nullptr;
+  double* d_Jc = nullptr;
+  void *d_phases = nullptr, *d_tiles = nullptr, *d_kinds = nullptr, *d_items_jac = nullptr, *d_items_hess = nullptr,
+       *d_items_aux = nullptr, *d_outer = nullptr, *d_items_hessc = nullptr;
+  double *d_aux = nullptr, *d_Hc = nullptr;
+  int32_t* d_ib = nullptr;
+  double* d_db = nullptr;
+  int64_t* d_lb = nullptr;
+  // work buffers
+  double *d_x = nullptr, *d_lam = nullptr, *d_f = nullptr, *d_grad = nullptr, *d_g = nullptr, *d_J = nullptr,
+         *d_H = nullptr, *d_I = nullptr, *d_partial = nullptr, *d_partial2 = nullptr;
+  std::vector<PkPhase> h_phases;
+  std::vector<int32_t> jac_row, jac_col, hess_row, hess_col;
+  // ---- the other areas
+  PkShard shard;
+  PkExchange exchange;
+  PkGraph graph;
+  PkProfile profile;
+  PkCsrMap csr[4];   // [0] Jacobian, [1] Hessian of the Lagrangian (lower triangle)
+                     // + [2]: compact Hessian values -> the same CSR entries (a pure permutation: one value per entry)
+                     // + [3]: compact Jacobian values -> the CSR entries of J (the few repeated positions summed)
+  PkMeshError mesh_error;
+  PkShim shim;
+};
+
+#pragma GCC visibility push(hidden)      // (no function declared here leaves the library: its exports are the two C headers')
+
+#define PK_HIP(c, call)                                                                                  \
+  do {                                                                                                   \
+    hipError_t e_ = (call);                                                                              \
+    if (e_ != hipSuccess) return fail((c), 100 + (int)e_, "%s failed: %s", #call, hipGetErrorString(e_)); \
+  } while (0)
+
+// ---- small helpers, inline in every unit
+template <class T>
+inline void release(T*& p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+inline int upload(pk_ctx* c, void** dst, const void* src, size_t bytes) {
+  *dst = nullptr;
+  const size_t alloc = bytes ? bytes : 8;
+  PK_HIP(c, hipMalloc(dst, alloc));
+  if (bytes) PK_HIP(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+
+inline int ready(pk_ctx* c) {
+  if (!c) return fail(nullptr, 1, "null context");
+  if (!c->have_model) return fail(c, 2, "no model loaded (pk_load_model)");
+  if (!c->have_problem) return fail(c, 3, "no problem set (pk_set_problem)");
+  return 0;
+}
+
+inline hipStream_t pick(pk_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
+
+// bytes of PkArgs the loaded code object declares: the head and as many phase records as it was compiled for
+inline size_t args_bytes(const pk_ctx* c) {
+  return offsetof(PkArgs, ph) + sizeof(PkPhase) * (size_t)(c->md.max_phases > 0 ? c->md.max_phases : 8);
+}
+
+// ---- pk_runtime.cpp: the launch machinery
+void drop_cycle_graph(pk_ctx* c);
+PkArgs base_args(pk_ctx* c, const double* d_x, const double* d_lam, double sigma);
+// pk_launch_shape with the facts of the context's problem (n_flat: entries of pk_csr / chunks of pk_runs; layout: pk_cyclec's)
+PkLaunchShape shape_of(const pk_ctx* c, int k, int64_t n_flat = 0, int layout = 0);
+int launch_raw(pk_ctx* c, int k, void* args, size_t sz, const PkLaunchShape& shape, hipStream_t st);
+int launch(pk_ctx* c, int k, PkArgs& A, hipStream_t st, int64_t n_flat = 0);
+int prepass(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f, bool write_f, hipStream_t st);
+int enqueue_single_launch_cycle(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f,
+                                double* d_grad, double* d_g, double* d_jac, double* d_hess, hipStream_t st, int layout = -1);
+bool xpart_is_one_launch(const pk_ctx* c);
+
+// ---- pk_shim.cpp: the per-callback path lives there; the core's one-shot host evaluation borrows these
+int alloc_shim(pk_ctx* c);      // pk_set_problem: staging buffers, landing places, events
+void free_shim(pk_ctx* c);
+int copy_async(pk_ctx* c, double* dst, const double* src, size_t n, hipMemcpyKind kind, bool by_kernel);
+int stage_upload(pk_ctx* c, double* const bufs[2], hipEvent_t const evs[2], uint64_t seqs[2], int& cur, const double* src,
+                 double* dst, size_t count, double** staged);
+int handoff_check(pk_ctx* c);
+int launch_store_word(pk_ctx* c, unsigned long long* dst, unsigned long long value, hipStream_t st);   // pk_store_word_kernel
+
+// ---- pk_extras.cpp
+void free_csr(pk_ctx* c);
+void free_mesh_error(pk_ctx* c);
+void free_trace(pk_ctx* c);
+
+// ---- the host-buffer form of an entry point: upload x (and lambda), the device-pointer entry point, download, synchronize
+inline int host_ready(pk_ctx* c, bool buffers) {
+  const int rc = ready(c);
+  return rc ? rc : buffers ? 0 : fail(c, 60, "null host buffer");
+}
+struct Download { double* host; const double* dev; size_t count; };
+
+// lambda == NULL: x alone goes up.  staged: the inputs go through the double-buffered pinned staging buffers of the host shim
+// (pk_eval_cycle) instead of a copy from the caller's arrays.  handoff: errors 97 of the fused cycle are reported.
+template <class Eval>
+int host_eval(pk_ctx* c, const double* x, const double* lambda, std::initializer_list<Download> results, bool handoff, Eval eval,
+              bool staged = false) {
+  int rc;
+  PK_HIP(c, hipSetDevice(c->device));
+  c->shim.x_valid = false;      // the context's x and result buffers now hold another evaluation
+  if (staged) {
+    if ((rc = stage_upload(c, c->shim.h_xs, c->shim.ev_xs, c->shim.xs_seq, c->shim.xbuf, x, c->d_x, (size_t)c->n, nullptr))) return rc;
+    if ((rc = stage_upload(c, c->shim.h_lams, c->shim.ev_lams, c->shim.lams_seq, c->shim.lambuf, lambda, c->d_lam, (size_t)c->m, nullptr))) return rc;
+  } else {
+    PK_HIP(c, hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    if (lambda) PK_HIP(c, hipMemcpyAsync(c->d_lam, lambda, sizeof(double) * (size_t)c->m, hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = eval())) return rc;
+  for (const Download& r : results)
+    PK_HIP(c, hipMemcpyAsync(r.host, r.dev, sizeof(double) * r.count, hipMemcpyDeviceToHost, c->stream));
+  PK_HIP(c, hipStreamSynchronize(c->stream));
+  return handoff ? handoff_check(c) : 0;
+}
+
+#pragma GCC visibility pop
+#endif  // PK_RUNTIME_H

@@ -1,6 +1,6 @@
 """Build helpers: the C-ABI runtime library and per-model gfx950 code objects.
 
-* ``build_runtime()``  hipcc -shared csrc/pk_runtime.cpp -> pockit_amd/libpockit_hip.so  (in-tree, so the
+* ``build_runtime()``  hipcc -shared csrc/<RUNTIME_SOURCES> -> pockit_amd/libpockit_hip.so  (in-tree, so the
   built library travels with the repository snapshot to the GPU box).
 * ``compile_model(source)``  generated HIP source -> code object for gfx950 (``hipcc --genco``), cached in
   pockit_amd/_cache/<sha>.hsaco keyed by the source hash.  The generated source is mesh-independent, so
@@ -45,12 +45,21 @@ def _stale(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
+# The files of the host runtime, stated once: build_runtime() compiles the sources and watches the headers, and
+# tests/test_runtime_sanitized.py builds its CPU-only binaries from the same lists.
+RUNTIME_SOURCES = [os.path.join(CSRC, name) for name in
+                   ("pk_runtime.cpp", "pk_shim.cpp", "pk_pool.cpp", "pk_shard.cpp", "pk_extras.cpp", "pk_error.cpp")]
+# (the helper-thread pool and the error slot it reports into: no HIP in either)
+POOL_SOURCES = [os.path.join(CSRC, name) for name in ("pk_pool.cpp", "pk_error.cpp")]
+RUNTIME_HEADERS = [os.path.join(CSRC, name) for name in
+                   ("pk_runtime.h", "pk_error.h", "pockit_hip_internal.h", "pk_abi.h", "pk_launch.h")] + [
+                       os.path.join(os.path.dirname(HERE), "include", "pockit_hip.h")]
+
+
 def build_runtime(force=False):
     """Compile libpockit_hip.so (host C++ against libamdhip64)."""
-    srcs = [os.path.join(CSRC, "pk_runtime.cpp"), os.path.join(CSRC, "pk_abi.h"), os.path.join(CSRC, "pk_launch.h"),
-            os.path.join(os.path.dirname(HERE), "include", "pockit_hip.h")]
-    if force or _stale(LIB_PATH, srcs):
-        _run([_hipcc(), f"--offload-arch={ARCH}", "-O2", "-fPIC", "-shared", "-std=c++17", srcs[0], "-o", LIB_PATH])
+    if force or _stale(LIB_PATH, RUNTIME_SOURCES + RUNTIME_HEADERS):
+        _run([_hipcc(), f"--offload-arch={ARCH}", "-O2", "-fPIC", "-shared", "-std=c++17"] + RUNTIME_SOURCES + ["-o", LIB_PATH])
     return LIB_PATH
 
 

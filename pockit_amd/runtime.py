@@ -1,4 +1,4 @@
-"""ctypes binding of libpockit_hip.so (the C ABI of include/pockit_hip.h).
+"""ctypes binding of libpockit_hip.so (the C ABI of include/pockit_hip.h and pockit_amd/csrc/pockit_hip_internal.h).
 
 Thin by design: structures, prototypes and error translation only.  A missing library, a missing
 GPU or a failing HIP call raises ``RuntimeError`` -- the package has no CPU evaluation path.
@@ -64,21 +64,107 @@ WAVES_PER_BLOCK = int(os.environ.get("POCKIT_AMD_WPB") or 4)  # PK_WAVES_PER_BLO
 WAVE = 64  # PK_WAVE
 KERNELS = ["pk_int", "pk_fin", "pk_g", "pk_grad", "pk_jac", "pk_hess", "pk_xall", "pk_aux", "pk_outer", "pk_hessc", "pk_err", "pk_csr",
            "pk_cycle", "pk_xchg", "pk_runs", "pk_jacc", "pk_cyclec"]
-EXPORTS = ["pk_create", "pk_destroy", "pk_last_error", "pk_device_count", "pk_load_model", "pk_set_problem",
-           "pk_get_structure", "pk_eval_f", "pk_eval_grad", "pk_eval_g", "pk_eval_jac", "pk_eval_hess",
-           "pk_eval_f_dev", "pk_eval_grad_dev", "pk_eval_g_dev", "pk_eval_jac_dev", "pk_eval_hess_dev",
-           "pk_eval_cycle_dev", "pk_eval_cycle_dev_repeat", "pk_eval_hessc_prepared", "pk_sync", "pk_profile", "pk_profile_read", "pk_kernel_name",
-           "pk_set_shard", "pk_eval_integrals_dev", "pk_eval_f_from_integrals_dev", "pk_aux_buffer", "pk_eval_outer_dev", "pk_store_word_dev", "pk_callback_cycle", "pk_eval_cycle",
-           "pk_prepare_x", "pk_fetch", "pk_eval_hess_prepared", "pk_host_buffer", "pk_eval_hessc", "pk_eval_hessc_dev",
-           "pk_set_mesh_error_tables", "pk_eval_mesh_error", "pk_eval_mesh_error_dev", "pk_set_cycle_graph", "pk_profile_sampling",
-           "pk_set_csr_map", "pk_gather_csr_dev", "pk_eval_jac_csr_dev", "pk_eval_hess_csr_dev", "pk_eval_jac_csr",
-           "pk_eval_hess_csr", "pk_trace_read", "pk_set_cycle_mode", "pk_same_x", "pk_set_result_targets",
-           "pk_result_location", "pk_set_host_mode", "pk_stage_lambda", "pk_invalidate_x", "pk_host_alloc", "pk_host_free",
-           "pk_device_alloc", "pk_device_free", "pk_ipc_export", "pk_ipc_open", "pk_ipc_close", "pk_set_shared_grad_target",
-           "pk_set_exchange", "pk_exchange_sums_dev", "pk_copy_runs_dev", "pk_set_exchange_inline",
-           "pk_host_register", "pk_host_unregister", "pk_copy_dev", "pk_eval_xpart_dev",
-           "pk_eval_jacc", "pk_eval_jacc_dev", "pk_callback_x", "pk_callback_hess", "pk_set_jac_constant_runs", "pk_fill_jac_constants", "pk_set_host_option",
-           "pk_set_jacobian_layout", "pk_exchange_status", "pk_wait_idle", "pk_same_bits", "pk_copy_bits", "pk_host_threads", "pk_host_threads_hot", "pk_host_threads_jobs", "pk_set_cycle_layout"]
+vp, dp = C.c_void_p, c_double_p
+# One prototype per export of libpockit_hip.so: name -> (restype, argtypes), grouped like the two C headers
+# (tests/test_cabi.py checks the table against them).
+PROTOTYPES = {
+    # ---- stable surface (include/pockit_hip.h)
+    "pk_create": (C.c_int, [C.POINTER(vp), C.c_int]),
+    "pk_destroy": (None, [vp]),
+    "pk_last_error": (C.c_char_p, [vp]),
+    "pk_device_count": (C.c_int, []),
+    "pk_load_model": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(ModelDesc)]),
+    "pk_set_problem": (C.c_int, [vp, C.POINTER(ProblemDesc)]),
+    "pk_get_structure": (C.c_int, [vp, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "pk_eval_f": (C.c_int, [vp, dp, dp]),
+    "pk_eval_grad": (C.c_int, [vp, dp, dp]),
+    "pk_eval_g": (C.c_int, [vp, dp, dp]),
+    "pk_eval_jac": (C.c_int, [vp, dp, dp]),
+    "pk_eval_hess": (C.c_int, [vp, dp, dp, C.c_double, dp]),
+    "pk_eval_cycle": (C.c_int, [vp, dp, dp, C.c_double, dp, dp, dp, dp, dp]),
+    "pk_eval_hessc": (C.c_int, [vp, dp, dp, C.c_double, dp]),
+    "pk_eval_jacc": (C.c_int, [vp, dp, dp]),
+    "pk_eval_jacc_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_eval_hessc_dev": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
+    "pk_set_mesh_error_tables": (C.c_int, [vp, vp, C.c_int32, vp, C.c_int32, dp, C.c_int64, C.c_int64]),
+    "pk_eval_mesh_error": (C.c_int, [vp, dp, dp, dp]),
+    "pk_eval_mesh_error_dev": (C.c_int, [vp, vp, vp, vp, vp]),
+    "pk_set_csr_map": (C.c_int, [vp, C.c_int, c_int32_p, c_int32_p, C.c_int64, C.c_int64]),
+    "pk_gather_csr_dev": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "pk_eval_jac_csr_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_eval_hess_csr_dev": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
+    "pk_eval_jac_csr": (C.c_int, [vp, dp, dp]),
+    "pk_eval_hess_csr": (C.c_int, [vp, dp, dp, C.c_double, dp]),
+    "pk_eval_f_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_eval_grad_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_eval_g_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_eval_jac_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_eval_hess_dev": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
+    "pk_eval_xpart_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    "pk_eval_cycle_dev": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]),
+    "pk_set_cycle_layout": (C.c_int, [vp, C.c_int, C.c_int]),
+    "pk_sync": (C.c_int, [vp, vp]),
+    # ---- host shim (csrc/pockit_hip_internal.h)
+    "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
+    "pk_same_x": (C.c_int, [vp, dp]),
+    "pk_prepare_x": (C.c_int, [vp, dp]),
+    "pk_fetch": (C.c_int, [vp, C.c_int, dp]),
+    "pk_eval_hess_prepared": (C.c_int, [vp, dp, C.c_double, dp]),
+    "pk_stage_lambda": (C.c_int, [vp, dp]),
+    "pk_set_result_targets": (C.c_int, [vp, dp, dp, dp, dp, dp]),
+    # (raw addresses on the per-callback entry points: building a typed pointer costs more than the call)
+    "pk_callback_x": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+    "pk_callback_hess": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, C.c_int, vp]),
+    "pk_callback_cycle": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, vp]),
+    "pk_set_jac_constant_runs": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pk_fill_jac_constants": (C.c_int, [vp, vp]),
+    "pk_set_host_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
+    "pk_set_jacobian_layout": (C.c_int, [vp, C.c_int]),
+    "pk_result_location": (C.c_int, [vp, C.c_int, C.POINTER(dp)]),
+    "pk_set_host_mode": (C.c_int, [vp, C.c_int, C.c_int]),
+    "pk_invalidate_x": (C.c_int, [vp]),
+    "pk_host_buffer": (C.c_int, [vp, C.c_int, C.POINTER(dp), C.POINTER(C.c_int64)]),
+    "pk_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(vp)]),
+    "pk_host_free": (C.c_int, [vp]),
+    # ---- helper threads (csrc/pockit_hip_internal.h)
+    "pk_same_bits": (C.c_int, [vp, vp, C.c_size_t]),
+    "pk_copy_bits": (C.c_int, [vp, vp, C.c_size_t]),
+    "pk_host_threads": (C.c_int, [C.c_int]),
+    "pk_host_threads_jobs": (C.c_long, []),
+    "pk_host_threads_hot": (C.c_int, []),
+    # ---- sharding (csrc/pockit_hip_internal.h)
+    "pk_set_shard": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    "pk_eval_integrals_dev": (C.c_int, [vp, vp, vp]),
+    "pk_aux_buffer": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int64)]),
+    "pk_eval_outer_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_eval_f_from_integrals_dev": (C.c_int, [vp, vp, vp, vp]),
+    "pk_device_alloc": (C.c_int, [vp, C.c_size_t, C.c_int, C.POINTER(vp)]),
+    "pk_device_free": (C.c_int, [vp, vp]),
+    "pk_ipc_export": (C.c_int, [vp, vp, vp]),
+    "pk_ipc_open": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "pk_ipc_close": (C.c_int, [vp, vp]),
+    "pk_set_shared_grad_target": (C.c_int, [vp, vp]),
+    "pk_host_register": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(vp)]),
+    "pk_host_unregister": (C.c_int, [vp, vp]),
+    "pk_copy_dev": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
+    "pk_set_exchange": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]),
+    "pk_exchange_status": (C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pk_exchange_sums_dev": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "pk_set_exchange_inline": (C.c_int, [vp, C.c_int]),
+    "pk_copy_runs_dev": (C.c_int, [vp, vp, C.c_int, vp, vp, vp]),
+    "pk_store_word_dev": (C.c_int, [vp, vp, C.c_int64, vp]),
+    # ---- tuning and diagnostics (csrc/pockit_hip_internal.h)
+    "pk_eval_cycle_dev_repeat": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "pk_set_cycle_graph": (C.c_int, [vp, C.c_int]),
+    "pk_set_cycle_mode": (C.c_int, [vp, C.c_int]),
+    "pk_wait_idle": (C.c_int, [vp, vp]),
+    "pk_profile": (C.c_int, [vp, C.c_int]),
+    "pk_profile_sampling": (C.c_int, [vp, C.c_int]),
+    "pk_trace_read": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int64]),
+    "pk_profile_read": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), dp]),
+    "pk_kernel_name": (C.c_char_p, [C.c_int]),
+}
+EXPORTS = list(PROTOTYPES)
 
 _lib = None
 
@@ -117,102 +203,9 @@ def load_library():
         lib = C.CDLL(path)
     except OSError as exc:
         raise RuntimeError(f"cannot load {path}: {exc}; the MI355X evaluator has no CPU fallback") from exc
-    vp, dp = C.c_void_p, c_double_p
-    lib.pk_create.argtypes = [C.POINTER(vp), C.c_int]
-    lib.pk_destroy.argtypes = [vp]
-    lib.pk_destroy.restype = None
-    lib.pk_last_error.argtypes = [vp]
-    lib.pk_last_error.restype = C.c_char_p
-    lib.pk_device_count.restype = C.c_int
-    lib.pk_load_model.argtypes = [vp, vp, C.c_size_t, C.POINTER(ModelDesc)]
-    lib.pk_set_problem.argtypes = [vp, C.POINTER(ProblemDesc)]
-    lib.pk_get_structure.argtypes = [vp, c_int32_p, c_int32_p, c_int32_p, c_int32_p]
-    lib.pk_eval_f.argtypes = [vp, dp, dp]
-    lib.pk_eval_grad.argtypes = [vp, dp, dp]
-    lib.pk_eval_g.argtypes = [vp, dp, dp]
-    lib.pk_eval_jac.argtypes = [vp, dp, dp]
-    lib.pk_eval_hess.argtypes = [vp, dp, dp, C.c_double, dp]
-    lib.pk_eval_cycle.argtypes = [vp, dp, dp, C.c_double, dp, dp, dp, dp, dp]
-    lib.pk_prepare_x.argtypes = [vp, dp]
-    lib.pk_fetch.argtypes = [vp, C.c_int, dp]
-    lib.pk_eval_hess_prepared.argtypes = [vp, dp, C.c_double, dp]
-    lib.pk_host_buffer.argtypes = [vp, C.c_int, C.POINTER(dp), C.POINTER(C.c_int64)]
-    lib.pk_same_x.argtypes = [vp, dp]
-    lib.pk_stage_lambda.argtypes = [vp, dp]
-    lib.pk_set_result_targets.argtypes = [vp, dp, dp, dp, dp, dp]
-    lib.pk_result_location.argtypes = [vp, C.c_int, C.POINTER(dp)]
-    lib.pk_set_host_mode.argtypes = [vp, C.c_int, C.c_int]
-    lib.pk_invalidate_x.argtypes = [vp]
-    lib.pk_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
-    lib.pk_host_free.argtypes = [vp]
-    lib.pk_device_alloc.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp)]
-    lib.pk_device_free.argtypes = [vp, vp]
-    lib.pk_ipc_export.argtypes = [vp, vp, vp]
-    lib.pk_ipc_open.argtypes = [vp, vp, C.POINTER(vp)]
-    lib.pk_ipc_close.argtypes = [vp, vp]
-    lib.pk_set_shared_grad_target.argtypes = [vp, vp]
-    lib.pk_set_exchange.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]
-    lib.pk_exchange_sums_dev.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.pk_copy_runs_dev.argtypes = [vp, vp, C.c_int, vp, vp, vp]
-    lib.pk_set_exchange_inline.argtypes = [vp, C.c_int]
-    lib.pk_host_register.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
-    lib.pk_host_unregister.argtypes = [vp, vp]
-    lib.pk_copy_dev.argtypes = [vp, vp, vp, C.c_size_t, vp]
-    lib.pk_eval_xpart_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    # (raw addresses on the per-callback entry points: building a typed pointer costs more than the call)
-    lib.pk_callback_x.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    lib.pk_callback_hess.argtypes = [vp, vp, vp, C.c_double, vp, vp, C.c_int, vp]
-    lib.pk_callback_cycle.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp]
-    lib.pk_set_jac_constant_runs.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.pk_fill_jac_constants.argtypes = [vp, vp]
-    lib.pk_set_host_option.argtypes = [vp, C.c_char_p, C.c_int]
-    lib.pk_set_jacobian_layout.argtypes = [vp, C.c_int]
-    lib.pk_exchange_status.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.pk_eval_hessc.argtypes = [vp, dp, dp, C.c_double, dp]
-    lib.pk_eval_jacc.argtypes = [vp, dp, dp]
-    lib.pk_eval_jacc_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_eval_hessc_dev.argtypes = [vp, vp, vp, C.c_double, vp, vp]
-    lib.pk_set_mesh_error_tables.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, dp, C.c_int64, C.c_int64]
-    lib.pk_eval_mesh_error.argtypes = [vp, dp, dp, dp]
-    lib.pk_eval_mesh_error_dev.argtypes = [vp, vp, vp, vp, vp]
-    lib.pk_set_cycle_graph.argtypes = [vp, C.c_int]
-    lib.pk_set_cycle_mode.argtypes = [vp, C.c_int]
-    lib.pk_set_cycle_layout.argtypes = [vp, C.c_int, C.c_int]
-    lib.pk_profile_sampling.argtypes = [vp, C.c_int]
-    lib.pk_set_csr_map.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, C.c_int64, C.c_int64]
-    lib.pk_gather_csr_dev.argtypes = [vp, C.c_int, vp, vp, vp]
-    lib.pk_eval_jac_csr_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_eval_hess_csr_dev.argtypes = [vp, vp, vp, C.c_double, vp, vp]
-    lib.pk_eval_jac_csr.argtypes = [vp, dp, dp]
-    lib.pk_eval_hess_csr.argtypes = [vp, dp, dp, C.c_double, dp]
-    lib.pk_trace_read.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64]
-    lib.pk_eval_f_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_eval_grad_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_eval_g_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_eval_jac_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_eval_hess_dev.argtypes = [vp, vp, vp, C.c_double, vp, vp]
-    lib.pk_eval_cycle_dev.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]
-    lib.pk_eval_hessc_prepared.argtypes = [vp, dp, C.c_double, dp, C.c_int]
-    lib.pk_eval_cycle_dev_repeat.argtypes = [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
-    lib.pk_sync.argtypes = [vp, vp]
-    lib.pk_wait_idle.argtypes = [vp, vp]
-    lib.pk_same_bits.argtypes = [vp, vp, C.c_size_t]
-    lib.pk_copy_bits.argtypes = [vp, vp, C.c_size_t]
-    lib.pk_host_threads.argtypes = [C.c_int]
-    lib.pk_host_threads_jobs.restype = C.c_long
-    lib.pk_set_shard.argtypes = [vp, C.c_int, C.c_int, vp]
-    lib.pk_eval_integrals_dev.argtypes = [vp, vp, vp]
-    lib.pk_eval_f_from_integrals_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_aux_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
-    lib.pk_eval_outer_dev.argtypes = [vp, vp, vp, vp]
-    lib.pk_store_word_dev.argtypes = [vp, vp, C.c_int64, vp]
-    lib.pk_profile.argtypes = [vp, C.c_int]
-    lib.pk_profile_read.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp]
-    lib.pk_kernel_name.argtypes = [C.c_int]
-    lib.pk_kernel_name.restype = C.c_char_p
-    for name in EXPORTS:
-        if name not in ("pk_destroy", "pk_last_error", "pk_kernel_name"):
-            getattr(lib, name).restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -1,4 +1,4 @@
-// driver.cpp -- TEST INFRASTRUCTURE: drives the host runtime behind the C ABI (pockit_amd/csrc/pk_runtime.cpp, compiled with
+// driver.cpp -- TEST INFRASTRUCTURE: drives the host runtime behind the C ABI (pockit_amd/csrc/pk_runtime.cpp and its sibling units, compiled with
 // -fsanitize=address,undefined against the host-only HIP stand-in of this directory) through the protocols a solver-side shim
 // uses: landing blocks, constant Jacobian runs, the prepared-x callbacks in any order, every switch of the shim, the speculative
 // Hessian on a matching and on a new x, pageable targets, the compact layouts, the one-call cycle, the per-callback host entry
@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/pockit_hip.h"
+#include "../../pockit_amd/csrc/pockit_hip_internal.h"
 #include "../../pockit_amd/csrc/pk_abi.h"
 #include "fake_hip.h"
 

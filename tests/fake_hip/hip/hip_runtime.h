@@ -1,5 +1,5 @@
-// hip_runtime.h -- TEST INFRASTRUCTURE: a host-only stand-in for the dozen HIP runtime calls pockit_amd/csrc/pk_runtime.cpp
-// uses, so that the host runtime (pinned rings, double-buffered staging, prepared-x protocol, copy batching, polling waits)
+// hip_runtime.h -- TEST INFRASTRUCTURE: a host-only stand-in for the dozen HIP runtime calls the units of the host runtime
+// (pockit_amd/csrc/pk_runtime.cpp, pk_shim.cpp, pk_shard.cpp, pk_extras.cpp) use, so that the host runtime (pinned rings, double-buffered staging, prepared-x protocol, copy batching, polling waits)
 // can be built with -fsanitize=address,undefined and driven on the CPU (tests/fake_hip/driver.cpp, tests/test_runtime_sanitized.py).
 // Never on a GPU, never part of the product.
 //

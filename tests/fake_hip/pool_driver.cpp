@@ -1,6 +1,6 @@
-// Driver of the host helper-thread pool of pk_runtime.cpp (pk_host_threads / pk_same_bits / pk_copy_bits) for the
+// Driver of the host helper-thread pool of pockit_amd/csrc/pk_pool.cpp (pk_host_threads / pk_same_bits / pk_copy_bits) for the
 // ThreadSanitizer build (tests/test_runtime_sanitized.py): passes of different lengths, helpers hot and cold, differences at
-// the front, in the middle and at the very end.  CPU only, no HIP call is made.
+// the front, in the middle and at the very end.  CPU only: built with pk_pool.cpp and pk_error.cpp alone, without HIP.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -9,7 +9,7 @@
 #include <thread>
 #include <vector>
 
-#include "include/pockit_hip.h"
+#include "pockit_amd/csrc/pockit_hip_internal.h"
 
 #define CHECK(cond)                                                              \
   do {                                                                           \

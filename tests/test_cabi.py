@@ -1,4 +1,5 @@
-"""The C-ABI library builds, loads and exports every symbol include/pockit_hip.h declares; without a
+"""The C-ABI library builds, loads and exports every symbol its two headers (include/pockit_hip.h, the stable surface, and
+pockit_amd/csrc/pockit_hip_internal.h) declare, and the ctypes prototypes agree with them; without a
 GPU the product fails loudly (no CPU fallback).  No compute calls are made here."""
 import ctypes as C
 import os
@@ -11,16 +12,52 @@ from pockit_amd import hipbuild, runtime
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+HEADERS = [os.path.join(ROOT, "include", "pockit_hip.h"), os.path.join(ROOT, "pockit_amd", "csrc", "pockit_hip_internal.h")]
+
+
+def _declarations(path):
+    """{name: (return type, [parameter declarations])} of the functions a C header declares (comments removed first)."""
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    found = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(pk_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        params = " ".join(params.split())
+        found[name] = (" ".join(ret.split()).replace(" *", "*"), [] if params in ("", "void") else [q.strip() for q in params.split(",")])
+    return found
+
+
 def test_library_exports_every_declared_symbol():
     hipbuild.build_runtime()
     lib = runtime.load_library()
-    header = open(os.path.join(ROOT, "include", "pockit_hip.h")).read()
-    declared = set(re.findall(r"\b(pk_[a-z_]+)\s*\(", header))
-    declared -= {"pk_ctx"}
-    assert declared, "no declarations parsed"
-    assert declared == set(runtime.EXPORTS)
-    for name in declared:
+    stable, internal = (set(_declarations(path)) for path in HEADERS)
+    assert stable and internal, "no declarations parsed"
+    assert not stable & internal, "a function is declared in both headers"
+    assert stable | internal == set(runtime.EXPORTS)
+    assert len(runtime.EXPORTS) == len(set(runtime.EXPORTS))
+    for name in stable | internal:
         assert getattr(lib, name) is not None
+
+
+def test_prototype_table_agrees_with_the_headers():
+    """runtime.PROTOTYPES against the declarations of both headers: the number of parameters, c_double exactly where the
+    header passes a double by value, and the return type (int; two const char*, one void, one long)."""
+    declared = {}
+    for path in HEADERS:
+        declared.update(_declarations(path))
+    assert set(declared) == set(runtime.PROTOTYPES)
+    returns = {"int": C.c_int, "const char*": C.c_char_p, "void": None, "long": C.c_long}
+    seen = []
+    for name, (ret, params) in declared.items():
+        restype, argtypes = runtime.PROTOTYPES[name]
+        assert len(argtypes) == len(params), name
+        by_value_double = [bool(re.match(r"^double\s+\w+$", q)) for q in params]
+        assert [t is C.c_double for t in argtypes] == by_value_double, name
+        assert ret in returns and restype is returns[ret], name
+        seen.append(ret)
+    assert (seen.count("const char*"), seen.count("void"), seen.count("long")) == (2, 1, 1)
+    lib = runtime.load_library()
+    for name, (restype, argtypes) in runtime.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
 
 
 def test_struct_sizes_match_the_c_abi():

@@ -1,4 +1,4 @@
-"""The host runtime behind the C ABI (pockit_amd/csrc/pk_runtime.cpp: pinned landing blocks, double-buffered staging,
+"""The host runtime behind the C ABI (the units of pockit_amd.hipbuild.RUNTIME_SOURCES: pinned landing blocks, double-buffered staging,
 prepared-x protocol, copy batching, polling waits, speculative Hessian, constant Jacobian runs, CSR run tables) built with
 ``-fsanitize=address,undefined`` against a host-only stand-in of the HIP runtime (tests/fake_hip: deferred streams, "kernels"
 that write recomputable values) and driven through its protocols by tests/fake_hip/driver.cpp.  CPU only -- GPU sanitizers are
@@ -8,6 +8,8 @@ import shutil
 import subprocess
 
 import pytest
+
+from pockit_amd.hipbuild import POOL_SOURCES, RUNTIME_SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = os.path.join(ROOT, "tests", "fake_hip")
@@ -21,9 +23,8 @@ def driver_exe(tmp_path_factory):
     """tests/fake_hip/driver.cpp + the runtime + the stand-in, built once with the address and undefined-behaviour sanitizers."""
     exe = str(tmp_path_factory.mktemp("runtime") / "pk_runtime_sanitized")
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-           "-fno-sanitize-recover=undefined", "-I", FAKE, "-I", ROOT,
-           os.path.join(ROOT, "pockit_amd", "csrc", "pk_runtime.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
-           os.path.join(FAKE, "driver.cpp"), "-o", exe]
+           "-fno-sanitize-recover=undefined", "-I", FAKE, "-I", ROOT] + RUNTIME_SOURCES + [
+               os.path.join(FAKE, "fake_hip.cpp"), os.path.join(FAKE, "driver.cpp"), "-o", exe]
     build = subprocess.run(cmd, capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-4000:]
     return exe
@@ -60,9 +61,8 @@ def test_host_helper_threads_under_sanitizers(tmp_path, sanitizer):
     lambda in the host-landed sharded cycle): ThreadSanitizer and AddressSanitizer builds of the same source, driven by
     tests/fake_hip/pool_driver.cpp through hot and cold helpers, every pass length class, differences at either end."""
     exe = str(tmp_path / "pk_pool_sanitized")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", f"-fsanitize={sanitizer}", "-fno-omit-frame-pointer", "-pthread", "-I", FAKE, "-I", ROOT,
-           os.path.join(ROOT, "pockit_amd", "csrc", "pk_runtime.cpp"), os.path.join(FAKE, "fake_hip.cpp"),
-           os.path.join(FAKE, "pool_driver.cpp"), "-o", exe]
+    cmd = ["g++", "-std=c++17", "-g", "-O1", f"-fsanitize={sanitizer}", "-fno-omit-frame-pointer", "-pthread", "-I", ROOT] + POOL_SOURCES + [
+               os.path.join(FAKE, "pool_driver.cpp"), "-o", exe]      # (the pool's two units alone: no stand-in of HIP needed)
     build = subprocess.run(cmd, capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-4000:]
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
