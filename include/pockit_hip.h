@@ -1,6 +1,6 @@
 /* pockit_hip.h -- C ABI of the MI355X NLP-callback evaluator (libpockit_hip.so).
  *
- * STABLE SURFACE.  The 35 entry points declared here are the contract of the library: what a second host binding for
+ * STABLE SURFACE.  The 38 entry points declared here are the contract of the library: what a second host binding for
  * pockit's evaluator path needs -- life cycle, evaluation on host buffers and on device pointers, the compact layouts, the CSR
  * hand-off and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
  * shim, the sharding transport, the helper threads, tuning switches and diagnostics) is declared in
@@ -215,6 +215,34 @@ int pk_eval_cycle_dev(pk_ctx* ctx, const double* d_x, const double* d_lambda, do
  * cycle stays ONE launch: the compact kernels' tile code runs in the Jacobian / Hessian roles of pk_cycle.  Error 69 for a
  * model whose system functions are nonlinear in the integrals or a mesh with an interval of more than 64 points. */
 int pk_set_cycle_layout(pk_ctx* ctx, int jac_compact, int hess_compact);
+
+/* A BATCH of iterates in one launch of the fused cycle (kernel pk_cycleb, blockIdx.y = batch entry): a caller that holds B
+ * iterates -- multi-start, a merit scan over trial points, a lock-step ensemble -- pays the fixed cost of a launch once per
+ * batch.  Entry b computes exactly what pk_eval_cycle_dev computes on (x_b, lambda_b, sigma_b), bit for bit.
+ *
+ * pk_load_batch_model attaches the model's BATCHED code object (pockit_amd.codegen.ModelSource(plan, batched=True): the same
+ * model code, pk_cycleb its only kernel) to a context that has its model; the descriptor is the model's.  Error 86: the object
+ * has no pk_cycleb.  code_object = NULL drops the batched object again.
+ * pk_set_batch allocates what a launch writes beside the caller's outputs once per entry (integrals, partial sums, hand-off
+ * slots, auxiliary buffer, staging rows) and the device array of B argument records; idempotent for the same B; a smaller B keeps the
+ * workspaces of the larger one (a context never shrinks them short of a new problem); freed with the problem.  Error 87: B outside 1 ... PK_MAX_BATCH.  pk_eval_cycle_batch_dev calls it where needed.
+ * pk_eval_cycle_batch_dev: all arrays are [B][...] row-major in device memory, rows of d_x / d_lambda ldx >= n / ldlambda >= m
+ * doubles apart, the outputs dense ([B], [B][n], [B][m], [B][nnz_J], [B][nnz_H]); ``sigma``: B values in HOST memory.
+ * d_lambda = NULL: an x-only batch (f, grad f, g, J; d_hess and sigma are not touched).  The argument records are written on
+ * the host (pinned memory of the context) and copied on ``stream`` ahead of the ONE launch, every call; a call waits for the
+ * record copy of the call before it, not for its kernel.  One batch or one single cycle may be in flight per context at a
+ * time; a hand-off that gives up in any entry is error 97 for the whole call (pk_sync), which puts the hand-off slots of
+ * every entry back to empty.
+ * Contexts whose cycle is not the one-launch cycle -- a model that needs the integrals first, the stand-alone kernels
+ * (separate_x), a shard, pk_set_cycle_mode(0), no batched object loaded -- are served by a loop of single cycles inside the
+ * call: the same values, no speed claim.  Error 88: a compact cycle layout, or a sharded context with the in-launch exchange.
+ * Error 89: a null pointer or a leading dimension that is too small. */
+#define PK_MAX_BATCH 64
+int pk_load_batch_model(pk_ctx* ctx, const void* code_object, size_t len);
+int pk_set_batch(pk_ctx* ctx, int B);
+int pk_eval_cycle_batch_dev(pk_ctx* ctx, int B, const double* d_x, int64_t ldx, const double* d_lambda, int64_t ldlambda,
+                            const double* sigma /* host, B values */, double* d_f, double* d_grad, double* d_g,
+                            double* d_jac, double* d_hess, void* stream);
 int pk_sync(pk_ctx* ctx, void* stream);
 
 #ifdef __cplusplus

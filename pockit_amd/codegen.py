@@ -266,8 +266,12 @@ class ModelSource:
     # lambda and the tables live there too, and the step was measured between 209 and 262 MB of outputs
     MALL_BYTES = 240_000_000
 
-    def __init__(self, plan: SystemPlan, sharded: bool = False, output_share: float = 1.0, group_cap=None, wide_nx=None):
-        """``wide_nx``: a phase with more states than this is evaluated the WIDE way (default WIDE_NX = 16; evaluator.compile_plan
+    def __init__(self, plan: SystemPlan, sharded: bool = False, output_share: float = 1.0, group_cap=None, wide_nx=None,
+                 batched: bool = False):
+        """``batched``: the source of the model's BATCHED code object, whose only kernel is pk_cycleb (B iterates per launch of the
+        fused cycle, ``Evaluator.cycle_batch``): the same model code, another kernel list.  It is an object of its own so that the
+        objects every evaluator needs keep their kernel list and compile time; compiled the first time a batch is asked for.
+        ``wide_nx``: a phase with more states than this is evaluated the WIDE way (default WIDE_NX = 16; evaluator.compile_plan
         lowers it to WIDE_NX_LOW for a pass-parallel model whose cycle kernel would otherwise leave room for one wave per SIMD
         only: the state-chunked values role needs far fewer registers)."""
         self.plan = plan
@@ -280,6 +284,9 @@ class ModelSource:
         # sharded: the finalize workgroup of pk_cycle carries the in-launch exchange of the partial sums between the GPUs.
         # Single-GPU code objects are compiled without it (its mere presence cost the 12k-node cycle 3 %).
         self.sharded = bool(sharded)
+        self.batched = bool(batched)
+        if self.batched and self.sharded:
+            raise ValueError("a batched code object has no in-launch exchange: batched and sharded exclude each other")
         self.nphase = len(plan.phase_plans)
         nI = len(plan.I_syms)
         # integrals evaluated by the pre-pass: those any system-level function references
@@ -977,6 +984,7 @@ class ModelSource:
         S.append("  __device__ static __forceinline__ void sys_grad_static(const PkSys& sy, double* g) { pkgen::sys_grad_static(sy, g); }")
         S.append("};")
         S.append("}  // namespace pkgen")
-        S.append("PK_DEFINE_KERNELS(pkgen::Gen)")
+        # (the batched object: the one-launch cycle over a batch of argument records, and nothing else)
+        S.append("PK_DEFINE_CYCLE_BATCH(pkgen::Gen)" if self.batched else "PK_DEFINE_KERNELS(pkgen::Gen)")
         return ("\n".join(S) + "\n").replace("//@PK_BIG_GLOBAL@", "#define PK_BIG_GLOBAL 1" if self.big_global else
                                                 "// (workgroup-wide intervals stage their rows in LDS)")

@@ -3881,6 +3881,23 @@ __device__ __forceinline__ void kernel_fin(const PkArgs& A) {
     pk::kernel_cycle<GEN, COMPACT>(pre_tile, pre_n_tiles, pre_flags, pre_grid, *(const PkArgs*)A_);                  \
   }
 
+/* pk_cycleb: B iterates in ONE launch of the fused cycle (a code object of its own: ModelSource(plan, batched=True)).
+   blockIdx.x is what it is in pk_cycle (pre_grid = gridDim.x: xcd_tile_block and every role are unchanged), blockIdx.y is the
+   batch entry.  The four preloaded scalars are the same for every entry and stay in the kernarg segment; the PkArgs of entry
+   b is record b of a device array the host wrote ahead of the launch.  The records are read-only for the whole launch, so
+   they are read through the constant address space like the kernarg segment is: uniform address -> scalar loads, and the
+   line prefetch at the top of kernel_cycle covers them.  What the indirection costs: ONE dependent scalar load (argv from
+   the kernarg segment, then the record) in front of the first field a wave reads -- the tile record does not need it
+   (pre_tile is preloaded), so the record's lines are in flight together with the tile record as before, one round trip
+   later than pk_cycle's.  Everything a launch writes is per entry (PkArgs.x ... big_stage); only the tables are shared. */
+#define PK_DEFINE_CYCLE_BATCH(GEN)                                                                                \
+  extern "C" __global__ __launch_bounds__(PK_BLOCK) void pk_cycleb(const PkTile* pre_tile, int32_t pre_n_tiles,   \
+                                                                   int32_t pre_flags, int32_t pre_grid,           \
+                                                                   const PkArgs* argv) {                          \
+    const PkArgs PK_CONST_AS* A_ = (const PkArgs PK_CONST_AS*)(uintptr_t)(argv + blockIdx.y);                      \
+    pk::kernel_cycle<GEN, false>(pre_tile, pre_n_tiles, pre_flags, pre_grid, *(const PkArgs*)A_);                   \
+  }
+
 #define PK_DEFINE_KERNELS(GEN)                                                                         \
   extern "C" __global__ __launch_bounds__(PK_BLOCK) void pk_int(PkArgs A) { pk::kernel_int<GEN>(A); }   \
   extern "C" __global__ __launch_bounds__(PK_BLOCK) void pk_fin(PkArgs A) { pk::kernel_fin<GEN>(A); }   \

@@ -10,10 +10,13 @@
 #include "pk_abi.h"
 
 enum { K_INT = 0, K_FIN, K_G, K_GRAD, K_JAC, K_HESS, K_XALL, K_AUX, K_OUTER, K_HESSC, K_ERR, K_CSR, K_CYCLE, K_XCHG, K_RUNS, K_JACC,
-       K_CYCLEC, K_COUNT };
+       K_CYCLEC, K_CYCLEB, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"pk_int", "pk_fin", "pk_g", "pk_grad", "pk_jac", "pk_hess", "pk_xall",
                                                   "pk_aux", "pk_outer", "pk_hessc", "pk_err", "pk_csr", "pk_cycle", "pk_xchg",
-                                                  "pk_runs", "pk_jacc", "pk_cyclec"};
+                                                  "pk_runs", "pk_jacc", "pk_cyclec", "pk_cycleb"};
+// pk_cycleb lives in a code object of its own (codegen.ModelSource(plan, batched=True), pk_load_batch_model): every other
+// kernel is looked up in the model's object by pk_load_model, this one never is
+inline bool pk_kernel_of_batched_object(int k) { return k == K_CYCLEB; }
 
 #define PK_LDS_LIMIT ((size_t)160 * 1024)      // LDS a workgroup may ask for on gfx950
 
@@ -28,7 +31,9 @@ struct PkLaunchFacts {
   int64_t n_flat = 0;        // pk_csr: CSR entries; pk_runs: chunks
 };
 
-struct PkLaunchShape { unsigned grid; size_t lds_bytes; };      // workgroups of PK_BLOCK threads, dynamic LDS per workgroup
+// workgroups of PK_BLOCK threads, dynamic LDS per workgroup; batch: the y-extent of the grid (pk_cycleb: the batch entries, set
+// by the launch -- the table knows the shape of ONE entry)
+struct PkLaunchShape { unsigned grid; size_t lds_bytes; unsigned batch = 1; };
 
 inline PkLaunchShape pk_launch_shape(int k, const pk_model_desc& md, const PkLaunchFacts& p) {
   const size_t D = sizeof(double), W = PK_WAVES_PER_BLOCK;
@@ -50,7 +55,7 @@ inline PkLaunchShape pk_launch_shape(int k, const pk_model_desc& md, const PkLau
     case K_HESSC: return {blocks * subs(md.hessc_subs) + 1, tile(md.lds_g, md.ne_hc)};      // (rows: the tile's multipliers)
     case K_JACC: return {blocks * subs(md.jacc_subs) + 1, tile(md.lds_jc, md.ne_jc)};
     case K_XALL: return {(p.split_xall ? 2u : 1u) * blocks + 1, tile(md.lds_x, md.ne_j)};
-    case K_CYCLE: case K_CYCLEC: {
+    case K_CYCLE: case K_CYCLEC: case K_CYCLEB: {      // (pk_cycleb: pk_cycle's x-grid and LDS, once per batch entry)
       // [edge J | edge H | finalize | per tile block: Jacobian, values, Hessian (x-part split) or x-part, Hessian; a model
       // evaluated in groups: the values workgroup and one per pass of the Jacobian / Hessian role (md.cycle_subs)]
       const unsigned per_block = md.cycle_subs > 0 ? (unsigned)md.cycle_subs : (p.split_xall ? 3u : 2u);

@@ -14,6 +14,7 @@
 //   eval_g     [pk_int, pk_fin(integrals)]?  pk_g
 //   eval_jac   [pk_int, pk_fin(integrals)]?  pk_jac
 //   eval_hess  [pk_int, pk_fin(integrals)]?  pk_hess
+//   batch      pk_cycleb: B cycles in ONE launch, a code object of its own (pk_batch.cpp)
 //   cycle      pk_cycle: ONE launch holding pk_xall's workgroups (f partials, grad f, g, J from one node
 //              evaluation), pk_hess's workgroups and a finalize workgroup that receives the partial sums of
 //              the same launch through hand-off slots (integrals, f, shared gradient slots);
@@ -45,6 +46,7 @@ void free_problem(pk_ctx* c) {
   release(c->d_x); release(c->d_lam); release(c->d_f); release(c->d_J);
   release(c->d_H); release(c->d_I); release(c->d_partial); release(c->d_partial2);
   release(c->d_cpart); release(c->d_cpart2);
+  free_batch(c);
   free_shim(c);
   c->have_problem = false;
 }
@@ -97,12 +99,12 @@ int launch_raw(pk_ctx* c, int k, void* args, size_t sz, const PkLaunchShape& sha
       PK_HIP(c, hipEventCreate(&ev.a));
       PK_HIP(c, hipEventCreate(&ev.b));
     }
-    PK_HIP(c, hipExtModuleLaunchKernel(c->fn[k], grid * PK_BLOCK, 1, 1, PK_BLOCK, 1, 1, shape.lds_bytes, st, nullptr, config,
+    PK_HIP(c, hipExtModuleLaunchKernel(c->fn[k], grid * PK_BLOCK, shape.batch, 1, PK_BLOCK, 1, 1, shape.lds_bytes, st, nullptr, config,
                                        ev.a, ev.b, 0));
     c->profile.pending[k].push_back(ev);
     return 0;
   }
-  PK_HIP(c, hipModuleLaunchKernel(c->fn[k], grid, 1, 1, PK_BLOCK, 1, 1, (unsigned)shape.lds_bytes, st, nullptr, config));
+  PK_HIP(c, hipModuleLaunchKernel(c->fn[k], grid, shape.batch, 1, PK_BLOCK, 1, 1, (unsigned)shape.lds_bytes, st, nullptr, config));
   return 0;
 }
 
@@ -136,9 +138,8 @@ static int prepass_if(pk_ctx* c, int32_t needed, const double* d_x, const double
 // (d_lam == NULL: the x-part alone -- the Hessian workgroups of the grid leave at once)
 // layout: bit 0 -- d_jac receives the COMPACT Jacobian (the Jacobian role of the launch runs pk_jacc's tile code), bit 1 --
 // d_hess receives the COMPACT Hessian (the Hessian workgroups run pk_hessc's); -1: what pk_set_cycle_layout chose
-int enqueue_single_launch_cycle(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f,
-                                double* d_grad, double* d_g, double* d_jac, double* d_hess, hipStream_t st, int layout) {
-  if (layout < 0) layout = c->cycle_layout;
+PkArgs cycle_args(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f, double* d_grad, double* d_g,
+                  double* d_jac, double* d_hess, int layout) {
   PkArgs A = base_args(c, d_x, d_lam, sigma);
   if (!d_lam) A.flags |= F_NO_HESS;
   A.o_f = d_f; A.o_grad = d_grad; A.o_g = d_g; A.o_jac = d_jac; A.o_hess = d_hess;
@@ -154,6 +155,13 @@ int enqueue_single_launch_cycle(pk_ctx* c, const double* d_x, const double* d_la
     A.xc_box = (unsigned long long* const*)c->exchange.box; A.xc_idx = c->exchange.idx;
     A.xc_world = c->exchange.world; A.xc_rank = c->exchange.rank; A.xc_epoch = 0; A.xc_nsh = c->exchange.nsh; A.xc_stride = c->exchange.stride;
   }      // (xc_epoch = 0: the cycle number is kept in device memory, so these arguments never change -> graph-replayable)
+  return A;
+}
+
+int enqueue_single_launch_cycle(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f,
+                                double* d_grad, double* d_g, double* d_jac, double* d_hess, hipStream_t st, int layout) {
+  if (layout < 0) layout = c->cycle_layout;
+  const PkArgs A = cycle_args(c, d_x, d_lam, sigma, d_f, d_grad, d_g, d_jac, d_hess, layout);
   // (the compact layouts: pk_cyclec, the same launch compiled with their roles -- a kernel of its own so that pk_cycle's
   //  register count stays what the reference layouts need)
   const int k = layout ? K_CYCLEC : K_CYCLE;
@@ -244,6 +252,7 @@ void pk_destroy(pk_ctx* c) {
     for (auto& ev : c->profile.pending[k]) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
   for (auto& ev : c->profile.free_events) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
   free_problem(c);
+  unload_batch_model(c);
   if (c->module) (void)hipModuleUnload(c->module);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -255,9 +264,11 @@ int pk_load_model(pk_ctx* c, const void* code_object, size_t len, const pk_model
   if (!c) return fail(nullptr, 1, "null context");
   if (!code_object || len == 0 || !md) return fail(c, 20, "pk_load_model: empty code object or descriptor");
   PK_HIP(c, hipSetDevice(c->device));
+  unload_batch_model(c);      // (a batched object belongs to the model it was generated from)
   if (c->module) { (void)hipModuleUnload(c->module); c->module = nullptr; c->have_model = false; }
   PK_HIP(c, hipModuleLoadData(&c->module, code_object));
-  for (int k = 0; k < K_COUNT; ++k) PK_HIP(c, hipModuleGetFunction(&c->fn[k], c->module, kKernelNames[k]));
+  for (int k = 0; k < K_COUNT; ++k)
+    if (!pk_kernel_of_batched_object(k)) PK_HIP(c, hipModuleGetFunction(&c->fn[k], c->module, kKernelNames[k]));
   c->md = *md;
   if (md->tab_cap != 64 && md->tab_cap != 256) return fail(c, 23, "pk_load_model: table capacity %d (64 or 256)", md->tab_cap);
   if (md->cycle_subs < 0 || md->cycle_subs > 4096) return fail(c, 25, "pk_load_model: cycle_subs %d", md->cycle_subs);
@@ -326,6 +337,7 @@ int pk_set_problem(pk_ctx* c, const pk_problem_desc* pd) {
     }
     release(c->d_big_stage);
     c->big_row = c->big_slot = 0;
+    c->big_stage_doubles = 0;
     if (n_stage) {
       size_t rows = (size_t)(c->md.lds_x > c->md.lds_h ? c->md.lds_x : c->md.lds_h) / PK_WAVE;
       if ((size_t)c->md.lds_jc / PK_WAVE > rows) rows = (size_t)c->md.lds_jc / PK_WAVE;
@@ -334,7 +346,8 @@ int pk_set_problem(pk_ctx* c, const pk_problem_desc* pd) {
       const size_t slot = rows * (size_t)c->big_row;
       if (slot > (size_t)INT32_MAX) return fail(c, 33, "pk_set_problem: an interval with %d points is too long for the staging buffer", kmax);
       c->big_slot = (int32_t)slot;
-      PK_HIP(c, hipMalloc((void**)&c->d_big_stage, sizeof(double) * slot * 4 * (size_t)n_stage));
+      c->big_stage_doubles = slot * 4 * (size_t)n_stage;
+      PK_HIP(c, hipMalloc((void**)&c->d_big_stage, sizeof(double) * c->big_stage_doubles));
     }
     if ((rc = upload(c, &c->d_tiles, tiles.data(), sizeof(PkTile) * tiles.size()))) return rc;
   }

@@ -4,6 +4,7 @@
 //   pk_shim.cpp     host shim: prepared-x protocol, landing blocks, copy batching, polling waits, its A/B options
 //   pk_pool.cpp     helper threads of the host's passes over x and lambda (no HIP, no pk_ctx: includes pk_error.h only)
 //   pk_shard.cpp    sharding: shard flags, peer / IPC / registered memory, the exchange of the partial sums, run copies
+//   pk_batch.cpp    a batch of iterates in one launch of the fused cycle (pk_cycleb): batched object, per-entry workspaces
 //   pk_extras.cpp   CSR hand-off, mesh error estimation, profiling and developer tracing
 //   pk_error.cpp    fail(): where an error message is kept
 //
@@ -75,6 +76,23 @@ struct PkGraph {
   hipGraphExec_t rep_exec = nullptr;      // pk_eval_cycle_dev_repeat: a batch of rep_count cycles as one graph
   int rep_count = 0;
   PkCycleKey cyc_key{}, rep_key{};
+};
+
+// ---- a batch of iterates per launch (pk_batch.cpp: pk_load_batch_model, pk_set_batch, pk_eval_cycle_batch_dev; free_batch)
+// Everything a launch of pk_cycleb writes beside the caller's outputs exists once per batch entry: nothing is shared between
+// the entries of a launch but the read-only tables and the status words.
+struct PkBatch {
+  hipModule_t module = nullptr;          // the batched code object (its only kernel: pk_cycleb = pk_ctx.fn[K_CYCLEB])
+  int B = 0, cap = 0;                    // entries armed by pk_set_batch; entries the workspaces were allocated for
+  double* d_ws = nullptr;                // per entry [integrals | partial | partial2 | auxiliary buffer], ws_stride doubles
+  unsigned long long* d_cp = nullptr;    // per entry [cpart | cpart2] hand-off slots (PK_EMPTY between launches)
+  double* d_big = nullptr;               // per entry the staging rows of intervals with more than 256 points
+  char* d_args = nullptr;                // the PkArgs records of the entries: what pk_cycleb's fifth argument points to
+  size_t ws_stride = 0, n_partial = 0, big_stride = 0;
+  char* h_args = nullptr;                // pinned: the records as filled on the host, copied to d_args ahead of every launch
+  hipEvent_t ev_copied = nullptr;        // ... recorded behind that copy: the next batch waits for it before it refills h_args
+  bool copy_pending = false;
+  int64_t launches = 0;                  // launches of pk_cycleb by this context (pk_batch_launches): the loop of single cycles adds none
 };
 
 // ---- profiling and developer tracing (pk_extras.cpp: free_trace; the timed launch itself is launch_raw's)
@@ -212,6 +230,7 @@ struct pk_ctx : pk_error_state {
   // staging rows of intervals with more than 256 points (they do not fit the workgroup's LDS rows): slots in device memory
   double* d_big_stage = nullptr;
   int32_t big_row = 0, big_slot = 0;
+  size_t big_stage_doubles = 0; // size of d_big_stage (pk_set_batch gives every batch entry a slice of its own)
   unsigned long long *d_cpart = nullptr, *d_cpart2 = nullptr;   // pk_cycle's hand-off slots (PK_EMPTY between launches)
   size_t cpart_slots = 0;
   int debug_flags = 0;          // diagnostic kernel switches (POCKIT_AMD_DEBUG_FLAGS), never set in production
@@ -239,6 +258,7 @@ struct pk_ctx : pk_error_state {
   PkShard shard;
   PkExchange exchange;
   PkGraph graph;
+  PkBatch batch;
   PkProfile profile;
   PkCsrMap csr[4];   // [0] Jacobian, [1] Hessian of the Lagrangian (lower triangle)
                      // + [2]: compact Hessian values -> the same CSR entries (a pure permutation: one value per entry)
@@ -292,6 +312,10 @@ PkLaunchShape shape_of(const pk_ctx* c, int k, int64_t n_flat = 0, int layout = 
 int launch_raw(pk_ctx* c, int k, void* args, size_t sz, const PkLaunchShape& shape, hipStream_t st);
 int launch(pk_ctx* c, int k, PkArgs& A, hipStream_t st, int64_t n_flat = 0);
 int prepass(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f, bool write_f, hipStream_t st);
+// the PkArgs of one single-launch cycle (flags, items of the layout, exchange): what pk_cycle / pk_cyclec take by value and
+// pk_cycleb reads from the record of a batch entry
+PkArgs cycle_args(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f, double* d_grad, double* d_g,
+                  double* d_jac, double* d_hess, int layout);
 int enqueue_single_launch_cycle(pk_ctx* c, const double* d_x, const double* d_lam, double sigma, double* d_f,
                                 double* d_grad, double* d_g, double* d_jac, double* d_hess, hipStream_t st, int layout = -1);
 bool xpart_is_one_launch(const pk_ctx* c);
@@ -304,6 +328,10 @@ int stage_upload(pk_ctx* c, double* const bufs[2], hipEvent_t const evs[2], uint
                  double* dst, size_t count, double** staged);
 int handoff_check(pk_ctx* c);
 int launch_store_word(pk_ctx* c, unsigned long long* dst, unsigned long long value, hipStream_t st);   // pk_store_word_kernel
+
+// ---- pk_batch.cpp
+void free_batch(pk_ctx* c);         // the per-entry workspaces (with the problem)
+void unload_batch_model(pk_ctx* c); // the batched code object (with the model)
 
 // ---- pk_extras.cpp
 void free_csr(pk_ctx* c);

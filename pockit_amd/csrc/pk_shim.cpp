@@ -89,6 +89,10 @@ int handoff_check(pk_ctx* c) {
     (void)hipMemcpy(c->d_cpart, empty.data(), sizeof(unsigned long long) * c->cpart_slots, hipMemcpyHostToDevice);
     (void)hipMemcpy(c->d_cpart2, empty.data(), sizeof(unsigned long long) * c->cpart_slots, hipMemcpyHostToDevice);
   }
+  if (c->batch.d_cp && c->batch.cap) {      // (the slots of every entry of a batch: the status words do not say which entry gave up)
+    const std::vector<unsigned long long> empty(2 * c->batch.n_partial * (size_t)c->batch.cap, (unsigned long long)PK_EMPTY);
+    (void)hipMemcpy(c->batch.d_cp, empty.data(), sizeof(unsigned long long) * empty.size(), hipMemcpyHostToDevice);
+  }
   c->shim.status_seen[0] = st[0];
   c->shim.status_seen[1] = st[1];
   c->shim.x_valid = false;

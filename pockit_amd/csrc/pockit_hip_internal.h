@@ -199,6 +199,9 @@ int pk_profile_sampling(pk_ctx* ctx, int period);
 int pk_trace_read(pk_ctx* ctx, uint64_t* out, int64_t count);
 int pk_profile_read(pk_ctx* ctx, int kernel_id, int64_t* launches, double* total_ms);
 const char* pk_kernel_name(int kernel_id);
+/* launches of pk_cycleb by this context so far (counted with or without profiling): a batch served by the loop of single
+ * cycles adds none, a batch served by the kernel adds exactly one */
+int pk_batch_launches(pk_ctx* ctx, int64_t* launches);
 
 #ifdef __cplusplus
 }

@@ -348,6 +348,17 @@ def compile_plan(plan: SystemPlan, sharded=False, output_share=1.0, extra_flags=
     return best[0], best[1]
 
 
+def batched_source(plan, src, output_share=1.0):
+    """The source of the BATCHED code object that goes with ``src`` (what ``compile_plan`` chose for the plan): the same model
+    code -- group size, wide threshold, store policy -- with ``pk_cycleb`` as its only kernel."""
+    return ModelSource(plan, output_share=output_share, group_cap=src.group_cap, wide_nx=src.wide_nx, batched=True)
+
+
+def compile_batched(plan, src, output_share=1.0, extra_flags=()):
+    """Code object of ``batched_source``; compiled and cached like any other the first time a batch is asked for."""
+    return hipbuild.compile_model(batched_source(plan, src, output_share).source, fastmath=plan.system._fastmath, extra_flags=extra_flags)
+
+
 class Evaluator:
     #: the one build change with evidence behind it for the round-5 defect (DESIGN.md section 11): SGPR spills to scratch memory
     SGPR_TO_SCRATCH = ("-mllvm", "-amdgpu-spill-sgpr-to-vgpr=0")
@@ -425,6 +436,9 @@ class Evaluator:
         self.hipcc_flags = tuple(hipcc_flags)
         self.separate_x = False      # (True: Evaluator.checked switched this context to the stand-alone kernels)
         self._want_host_helpers = bool(host_helpers) and tile_filter is None
+        self._output_share = float(output_share)
+        self._batch_state = None     # None: not decided; "kernel": pk_cycleb loaded and verified; "loop": single cycles (see _ensure_batch)
+        self._batch_bufs = (0, None)
         # (compiled before the context is created: a box without a GPU -- the build container -- can still fill the
         # code-object cache by constructing evaluators, tools/warm_cache.sh)
         self.src, code = compile_plan(plan, sharded=sharded, output_share=output_share, extra_flags=self.hipcc_flags, fixed=_fixed)
@@ -480,6 +494,7 @@ class Evaluator:
 
     def close(self):
         if self.ctx is not None:
+            self._free_batch_buffers()
             self.ctx.close()
             self.ctx = None
 
@@ -875,6 +890,179 @@ class Evaluator:
 
     def sync(self, stream=None):
         self.ctx.check(self.ctx.lib.pk_sync(self.ctx.handle, stream))
+
+    # ------------------------------------------------------------------ a batch of iterates per launch (pk_cycleb)
+    def batched_source(self):
+        """The source of this model's batched code object: the model code of ``self.src``, ``pk_cycleb`` its only kernel."""
+        return batched_source(self.plan, self.src, self._output_share)
+
+    def _one_launch_cycle(self):
+        """Is this context's cycle the one-launch cycle (what a batch can be one launch of)?"""
+        md = self.model_desc
+        return not (md.prepass_grad or md.prepass_g or md.prepass_jac or md.prepass_hess or self.separate_x or self.src.sharded)
+
+    def _ensure_batch(self):
+        """First batch of this evaluator: compile (or fetch) and load the batched code object, then hold it against this
+        context's own single launches.  The batched object is a new build of the fused kernel, so the set-up check of
+        ``pk_cycle`` (``Evaluator.checked``) says nothing about it: a batch of two -- the self-check's
+        probe point and a second point -- must agree BIT FOR BIT with two single cycles, and the x-only batch of the same points
+        with the single x-only path.  On any difference the object is dropped: batches are then served by the library's loop of
+        single cycles (the same values, no gain) and a ``RuntimeWarning`` names the model.  ``POCKIT_AMD_SELF_CHECK=0`` skips the
+        check (the object is used unchecked).  Models whose cycle is not the one-launch cycle take the loop from the start."""
+        if self._batch_state is not None:
+            return self._batch_state
+        if not self._one_launch_cycle():
+            self._batch_state = "loop"
+            return self._batch_state
+        lib, h = self.ctx.lib, self.ctx.handle
+        code = compile_batched(self.plan, self.src, self._output_share, self.hipcc_flags)
+        self.ctx.check(lib.pk_load_batch_model(h, code, len(code)))
+        self._batch_state = "kernel"
+        if os.environ.get("POCKIT_AMD_SELF_CHECK", "1") == "0":
+            return self._batch_state
+        rng = np.random.default_rng(20240531)                      # (entry 0: self_check's x and lambda, drawn in its order)
+        X, Lam = np.empty((2, self.plan.n)), np.empty((2, self.plan.m))
+        for e in range(2):
+            X[e] = 0.7 + 0.6 * rng.uniform(size=self.plan.n)
+            Lam[e] = rng.standard_normal(self.plan.m)
+        sig = np.array([1.0, 0.75])
+        names = ("f", "grad f", "g", "J", "H")
+        same = lambda a, b: np.array_equal(np.ascontiguousarray(a).reshape(-1).view(np.uint64),  # noqa: E731
+                                           np.ascontiguousarray(b, dtype=np.float64).reshape(-1).view(np.uint64))
+        worst = ""
+        try:
+            with np.errstate(all="ignore"):
+                got = self._cycle_batch_chunk(X, Lam, sig)
+                got_x = self._cycle_batch_chunk(X, None, sig)      # (the x-only records: no Hessian role)
+                for e in range(2):
+                    want = self._cycle_plain(X[e], Lam[e], sig[e])
+                    for name, a, b in zip(names, got, want):
+                        if not same(a[e], b):
+                            worst = worst or f"{name} of entry {e}"
+                    self._invalidate_x()
+                    x = X[e].copy()      # (the single x-only path: what the first callback on a new x launches)
+                    want_x = (self.objective(x), self.gradient(x), self.constraints(x), self.jacobian(x))
+                    for name, a, b in zip(names, got_x, want_x):
+                        if not same(a[e], b):
+                            worst = worst or f"{name} of entry {e} of the x-only batch"
+        finally:
+            self._invalidate_x()
+            self._free_batch_buffers()
+        if worst:
+            import warnings
+
+            self.ctx.check(lib.pk_load_batch_model(h, None, 0))
+            self._batch_state = "loop"
+            p = self.plan
+            warnings.warn(f"pockit_amd: the batched kernel (pk_cycleb) of model {self.src.hash} ({len(p.phase_plans)} phases, n = {p.n}, "
+                          f"m = {p.m}) differs from the single-launch cycle of the same context ({worst}): its code object is dropped, "
+                          "batches are served by a loop of single cycles (DESIGN.md sections 11 and 14)", RuntimeWarning, stacklevel=3)
+        return self._batch_state
+
+    def _cycle_plain(self, x, lam, sigma):
+        """One cycle through pk_eval_cycle into plain arrays: (f (1,), grad, g, J, H)."""
+        p, dp = self.plan, runtime.as_dp
+        x, lam = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(lam, dtype=np.float64)
+        f, grad, g, J, H = np.empty(1), np.empty(p.n), np.empty(p.m), np.empty(p.nnz_J), np.empty(p.nnz_H)
+        self.ctx.check(self.ctx.lib.pk_eval_cycle(self.ctx.handle, dp(x), dp(lam), float(sigma), dp(f), dp(grad), dp(g), dp(J), dp(H)))
+        return f, grad, g, J, H
+
+    def _free_batch_buffers(self):
+        cap, bufs = self._batch_bufs
+        if bufs and self.ctx is not None and self.ctx.handle:
+            for ptr in bufs.values():
+                self.ctx.lib.pk_device_free(self.ctx.handle, ptr)
+        self._batch_bufs = (0, None)
+
+    def _batch_buffers(self, B):
+        """Device arrays [B][...] of the host-array form: x, lambda and the five outputs -- kept from chunk to chunk of one
+        ``cycle_batch``, freed before it returns (64 entries of a large model are of the order of a gigabyte)."""
+        cap, bufs = self._batch_bufs
+        if bufs is not None and B <= cap:
+            return bufs
+        self._free_batch_buffers()
+        p, bufs = self.plan, {}
+        for name, count in (("x", p.n), ("lam", p.m), ("f", 1), ("grad", p.n), ("g", p.m), ("jac", p.nnz_J), ("hess", p.nnz_H)):
+            ptr = C.c_void_p()
+            self.ctx.check(self.ctx.lib.pk_device_alloc(self.ctx.handle, 8 * B * max(int(count), 1), 0, C.byref(ptr)))
+            bufs[name] = ptr.value
+        self._batch_bufs = (B, bufs)
+        return bufs
+
+    def _cycle_batch_chunk(self, X, Lam, sig):
+        """At most MAX_BATCH iterates: upload, ONE call of the library, download, wait."""
+        p, lib, h = self.plan, self.ctx.lib, self.ctx.handle
+        B = len(X)
+        d = self._batch_buffers(B)
+        self.ctx.check(lib.pk_copy_dev(h, d["x"], X.ctypes.data, X.nbytes, None))
+        if Lam is not None:
+            self.ctx.check(lib.pk_copy_dev(h, d["lam"], Lam.ctypes.data, Lam.nbytes, None))
+        self.ctx.check(lib.pk_eval_cycle_batch_dev(h, B, d["x"], p.n, d["lam"] if Lam is not None else None, p.m,
+                                                   runtime.as_dp(sig), d["f"], d["grad"], d["g"], d["jac"], d["hess"], None))
+        out = [np.empty(B), np.empty((B, p.n)), np.empty((B, p.m)), np.empty((B, p.nnz_J)),
+               np.empty((B, p.nnz_H)) if Lam is not None else None]
+        for name, a in zip(("f", "grad", "g", "jac", "hess"), out):
+            if a is not None:
+                self.ctx.check(lib.pk_copy_dev(h, a.ctypes.data, d[name], a.nbytes, None))
+        self.sync()
+        return out
+
+    def cycle_batch_dev(self, B, d_x, d_lam, sigmas, d_f, d_grad, d_g, d_jac, d_hess, stream=None):
+        """Enqueue the cycles of ``B`` iterates (at most ``runtime.MAX_BATCH``) on device pointers (ints) as ONE launch of
+        ``pk_cycleb``, without waiting for it.  (The FIRST batch of an evaluator loads the batched code object and holds it against
+        single launches -- ``_ensure_batch`` -- which compiles, evaluates and waits.)  The arrays are dense ``[B][...]``; ``sigmas``: B host values; ``d_lam = None``: an
+        x-only batch (``d_hess`` is not touched)."""
+        self._ensure_batch()
+        sig = np.ascontiguousarray(sigmas, dtype=np.float64).reshape(-1)
+        if d_lam is not None and len(sig) != int(B):
+            raise ValueError(f"sigmas must have {int(B)} values")
+        p = self.plan
+        self._invalidate_x()
+        self.ctx.check(self.ctx.lib.pk_eval_cycle_batch_dev(self.ctx.handle, int(B), d_x, p.n, d_lam, p.m, runtime.as_dp(sig) if len(sig) else None,
+                                                            d_f, d_grad, d_g, d_jac, d_hess, stream))
+
+    def cycle_batch(self, X, Lam=None, sigma=1.0):
+        """The cycles of the ``B`` iterates ``X[b], Lam[b], sigma[b]`` -- one launch per ``runtime.MAX_BATCH`` of them, every
+        entry bit for bit what ``cycle`` returns for it.  ``X``: (B, n); ``Lam``: (B, m), or None for the x-only outputs;
+        ``sigma``: a scalar or (B,).  Returns new arrays ``(f (B,), grad (B, n), g (B, m), J (B, nnz_J), H (B, nnz_H) or None)``.
+        Afterwards no iterate is the prepared one (as after ``cycle`` on plain arrays)."""
+        p = self.plan
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != p.n:
+            raise ValueError(f"X must have shape (B, {p.n})")
+        B = X.shape[0]
+        if Lam is not None:
+            Lam = np.ascontiguousarray(Lam, dtype=np.float64)
+            if Lam.shape != (B, p.m):
+                raise ValueError(f"Lam must have shape ({B}, {p.m})")
+        sig = np.asarray(sigma, dtype=np.float64)
+        if sig.ndim == 0:
+            sig = np.full(B, float(sig))
+        if sig.shape != (B,):
+            raise ValueError(f"sigma must be a scalar or have shape ({B},)")
+        sig = np.ascontiguousarray(sig)
+        out = [np.empty(B), np.empty((B, p.n)), np.empty((B, p.m)), np.empty((B, p.nnz_J)),
+               np.empty((B, p.nnz_H)) if Lam is not None else None]
+        if B == 0:
+            return tuple(out)
+        self._ensure_batch()
+        self._invalidate_x()        # the context's x / result buffers may hold other iterates afterwards
+        try:
+            for lo in range(0, B, runtime.MAX_BATCH):
+                hi = min(B, lo + runtime.MAX_BATCH)
+                part = self._cycle_batch_chunk(X[lo:hi], None if Lam is None else Lam[lo:hi], sig[lo:hi])
+                for a, b in zip(out, part):
+                    if a is not None:
+                        a[lo:hi] = b
+        finally:
+            self._free_batch_buffers()
+        return tuple(out)
+
+    def batch_launches(self):
+        """Launches of ``pk_cycleb`` by this evaluator so far: a batch served by the loop of single cycles adds none."""
+        n = C.c_int64()
+        self.ctx.check(self.ctx.lib.pk_batch_launches(self.ctx.handle, C.byref(n)))
+        return n.value
 
     def profile(self, enable=True, period=1):
         """Time the kernels whose bit is set in ``enable`` with HIP events; only every ``period``-th launch."""

@@ -669,6 +669,11 @@ class SystemBase:
             return self.evaluator.hessian_compact(x, lagrange, obj_factor)
         return self.evaluator.hessian(x, lagrange, obj_factor)
 
+    def evaluate_batch(self, X, Lam=None, sigma=1.0):
+        """f, grad f, g, J, H of the ``B`` iterates ``X[b], Lam[b], sigma[b]`` from one launch per 64 of them
+        (``Evaluator.cycle_batch``); ``Lam = None``: the x-only outputs, H is None.  Reference layouts."""
+        return self.evaluator.cycle_batch(X, Lam, sigma)
+
     # split Hessians used by the SciPy adapter (reference: systembase.py:726-809)
     def hessianstructure_o(self):
         if self._hessian_layout == "compact":

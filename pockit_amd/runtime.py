@@ -64,6 +64,8 @@ WAVES_PER_BLOCK = int(os.environ.get("POCKIT_AMD_WPB") or 4)  # PK_WAVES_PER_BLO
 WAVE = 64  # PK_WAVE
 KERNELS = ["pk_int", "pk_fin", "pk_g", "pk_grad", "pk_jac", "pk_hess", "pk_xall", "pk_aux", "pk_outer", "pk_hessc", "pk_err", "pk_csr",
            "pk_cycle", "pk_xchg", "pk_runs", "pk_jacc", "pk_cyclec"]
+BATCH_KERNEL = "pk_cycleb"      # the one kernel of a model's batched code object (codegen.ModelSource(plan, batched=True))
+MAX_BATCH = 64                  # PK_MAX_BATCH of include/pockit_hip.h: entries of one launch of it
 vp, dp = C.c_void_p, c_double_p
 # One prototype per export of libpockit_hip.so: name -> (restype, argtypes), grouped like the two C headers
 # (tests/test_cabi.py checks the table against them).
@@ -103,6 +105,9 @@ PROTOTYPES = {
     "pk_eval_xpart_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
     "pk_eval_cycle_dev": (C.c_int, [vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]),
     "pk_set_cycle_layout": (C.c_int, [vp, C.c_int, C.c_int]),
+    "pk_load_batch_model": (C.c_int, [vp, vp, C.c_size_t]),
+    "pk_set_batch": (C.c_int, [vp, C.c_int]),
+    "pk_eval_cycle_batch_dev": (C.c_int, [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, dp, vp, vp, vp, vp, vp, vp]),
     "pk_sync": (C.c_int, [vp, vp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
@@ -162,6 +167,7 @@ PROTOTYPES = {
     "pk_profile_sampling": (C.c_int, [vp, C.c_int]),
     "pk_trace_read": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pk_profile_read": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), dp]),
+    "pk_batch_launches": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "pk_kernel_name": (C.c_char_p, [C.c_int]),
 }
 EXPORTS = list(PROTOTYPES)
