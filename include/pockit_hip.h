@@ -1,6 +1,6 @@
 /* pockit_hip.h -- C ABI of the MI355X NLP-callback evaluator (libpockit_hip.so).
  *
- * STABLE SURFACE.  The 38 entry points declared here are the contract of the library: what a second host binding for
+ * STABLE SURFACE.  The 42 entry points declared here are the contract of the library: what a second host binding for
  * pockit's evaluator path needs -- life cycle, evaluation on host buffers and on device pointers, the compact layouts, the CSR
  * hand-off and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
  * shim, the sharding transport, the helper threads, tuning switches and diagnostics) is declared in
@@ -193,6 +193,25 @@ int pk_eval_hess_csr_dev(pk_ctx* ctx, const double* d_x, const double* d_lambda,
                          void* stream);
 int pk_eval_jac_csr(pk_ctx* ctx, const double* x, double* vals /* n_unique */);
 int pk_eval_hess_csr(pk_ctx* ctx, const double* x, const double* lambda, double sigma, double* vals);
+
+/* The matrices of the CSR hand-off applied to vectors on the device: y = A v (+ add) with A = J (op 0), J^T (op 1) or the
+ * symmetric H (op 2, from its lower triangle), the values read where pk_eval_*_csr_dev / pk_gather_csr_dev left them.
+ * An operator is a CSR structure (indptr, indices; int32) whose entry e takes its value from vals[src[e]] of the CSR value
+ * array of a map (src NULL: vals[e]): pockit_amd/csr.py builds the three from the maps (J itself; the transpose; L + L^T -
+ * diag(L), each off-diagonal entry twice with one src).  pk_set_csr_operator needs the matching pk_set_csr_map (which = 0 for
+ * op 0 / 1, which = 1 for op 2), checks everything a kernel will index with (errors 110-116, 119) and cuts the rows into
+ * the kernels' work items; pk_set_csr_map and pk_set_problem drop every operator.  Every y[row] is a fixed expression of the
+ * inputs (no atomics): the same bits from run to run.  ``d_add`` may be NULL and may alias ``d_y``.
+ * pk_linearize evaluates the CSR values of J at x -- and of H with (lambda, sigma) unless lambda is NULL -- into the
+ * context's own value arrays (the ones pk_eval_jac_csr / pk_eval_hess_csr use) and downloads nothing; pk_apply_operator
+ * sends v up, multiplies with that linearization and brings y down (error 118: no linearization, or none of H for op 2;
+ * 117: no operator).  A context holds one linearization: pk_eval_jac_csr / pk_eval_hess_csr and pk_set_csr_map end it. */
+int pk_set_csr_operator(pk_ctx* ctx, int op, const int32_t* indptr /* n_rows + 1 */, const int32_t* indices,
+                        const int32_t* src /* nnz or NULL */, int32_t n_rows, int32_t n_cols, int64_t nnz);
+int pk_apply_operator_dev(pk_ctx* ctx, int op, const double* d_vals, const double* d_v, const double* d_add, double* d_y,
+                          void* stream);
+int pk_linearize(pk_ctx* ctx, const double* x, const double* lambda /* or NULL */, double sigma);
+int pk_apply_operator(pk_ctx* ctx, int op, const double* v, double* y);
 
 /* device-pointer API: enqueue on ``stream`` (hipStream_t, NULL = context stream), no sync */
 int pk_eval_f_dev(pk_ctx* ctx, const double* d_x, double* d_f, void* stream);

@@ -3,6 +3,9 @@
 The NLP callbacks return values in the reference's triplet order (duplicates included, systembase.py:671-693,
 811-835).  A GPU linear solver wants CSR.  The (row, col) sort is a property of the mesh, so it is done once
 here; per iterate the device only gathers (``pk_csr``): ``csr[p] = sum(triplets[perm[seg[p]:seg[p+1]]])``.
+
+``CsrOperator``: the structures of the products ``J v``, ``J^T y``, ``H v`` on those values where they lie
+(``csrc/pk_ops.cpp``), built from a map: the matrix itself, its transpose and the symmetric completion of a lower triangle.
 """
 from __future__ import annotations
 
@@ -55,3 +58,54 @@ class CsrMap:
         import scipy.sparse
 
         return scipy.sparse.csr_array((np.asarray(values), self.indices, self.indptr), shape=self.shape)
+
+    # ---- operator structures of the device-side products (csrc/pk_ops.cpp): J . v, J^T . y, H . v
+    def operator(self):
+        """The matrix itself as a ``CsrOperator``: entry ``e`` takes ``values[e]``."""
+        return CsrOperator(self.shape, self.indptr, self.indices, None)
+
+    def transposed(self):
+        """CSR of the transpose; ``src`` points into this map's values (nothing is copied per iterate)."""
+        n_rows, n_cols = self.shape
+        rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(self.indptr))
+        order = np.argsort(self.indices, kind="stable")      # by column; rows stay ascending within one
+        indptr = np.searchsorted(self.indices[order], np.arange(n_cols + 1))
+        return CsrOperator((n_cols, n_rows), indptr, rows[order], order)
+
+    def symmetric(self):
+        """For a lower-triangular map: the full symmetric pattern ``L + L^T - diag(L)``.  An off-diagonal entry is
+        listed twice with the same ``src``, a diagonal entry once."""
+        n_rows, n_cols = self.shape
+        if n_rows != n_cols:
+            raise ValueError("symmetric(): the map is not square")
+        rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(self.indptr))
+        cols = self.indices.astype(np.int64)
+        if np.any(cols > rows):
+            raise ValueError("symmetric(): the map has an entry above the diagonal")
+        off = np.flatnonzero(cols < rows)
+        r, c = np.concatenate((rows, cols[off])), np.concatenate((cols, rows[off]))
+        src = np.concatenate((np.arange(self.nnz, dtype=np.int64), off))
+        order = np.argsort(r * n_cols + c, kind="stable")      # (no position repeats: L has one entry per position)
+        indptr = np.searchsorted(r[order], np.arange(n_rows + 1))
+        return CsrOperator(self.shape, indptr, c[order], src[order])
+
+
+class CsrOperator:
+    """CSR structure of a matrix whose entries are taken from the CSR value array of a ``CsrMap``: entry ``e`` has the value
+    ``values[src[e]]`` (``src`` None: ``values[e]``).  ``indptr`` (rows + 1), ``indices`` and ``src`` are int32, columns
+    ascending within a row.  What ``pk_set_csr_operator`` takes."""
+
+    def __init__(self, shape, indptr, indices, src):
+        self.shape = (int(shape[0]), int(shape[1]))
+        if len(indices) > np.iinfo(np.int32).max:
+            raise ValueError("pattern too large for 32-bit indices")
+        self.indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.src = None if src is None else np.ascontiguousarray(src, dtype=np.int32)
+        self.nnz = len(self.indices)
+
+    def to_scipy(self, values):
+        import scipy.sparse
+
+        v = np.asarray(values)
+        return scipy.sparse.csr_array((v if self.src is None else v[self.src], self.indices, self.indptr), shape=self.shape)

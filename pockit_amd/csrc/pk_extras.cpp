@@ -40,6 +40,7 @@ int pk_set_csr_map(pk_ctx* c, int which, const int32_t* seg, const int32_t* perm
   }
   PK_HIP(c, hipSetDevice(c->device));
   PK_HIP(c, hipStreamSynchronize(c->stream));
+  free_operators(c);      // (their src refers to a map, the linearization lies in the maps' value arrays)
   auto& m = c->csr[which];
   release(m.d_seg); release(m.d_perm); release(m.d_vals);
   m.n_unique = m.n_triplets = 0;
@@ -110,6 +111,7 @@ int pk_eval_jac_csr(pk_ctx* c, const double* x, double* vals) {
   if (const int rc = host_ready(c, x && vals)) return rc;
   const PkCsrMap& m = c->csr[c->csr[3].n_unique > 0 ? 3 : 0];      // (both maps fill the same CSR entries)
   if (m.n_unique == 0) return fail(c, 84, "pk_eval_jac_csr: call pk_set_csr_map first");
+  drop_linearization(c);      // (m.d_vals is where pk_linearize leaves J)
   return host_eval(c, x, nullptr, {{vals, m.d_vals, (size_t)m.n_unique}}, false,
                    [&] { return pk_eval_jac_csr_dev(c, c->d_x, m.d_vals, nullptr); });
 }
@@ -118,6 +120,7 @@ int pk_eval_hess_csr(pk_ctx* c, const double* x, const double* lambda, double si
   if (const int rc = host_ready(c, x && lambda && vals)) return rc;
   const PkCsrMap& m = c->csr[c->csr[2].n_unique > 0 ? 2 : 1];      // (both maps fill the same CSR entries)
   if (m.n_unique == 0) return fail(c, 84, "pk_eval_hess_csr: call pk_set_csr_map first");
+  drop_linearization(c);
   return host_eval(c, x, lambda, {{vals, m.d_vals, (size_t)m.n_unique}}, false,
                    [&] { return pk_eval_hess_csr_dev(c, c->d_x, c->d_lam, sigma, m.d_vals, nullptr); });
 }

@@ -1,0 +1,301 @@
+// pk_ops.cpp -- the matrices of the CSR hand-off applied to vectors where their values lie: y = J v, y = J^T v and
+// y = H v (H symmetric, stored as its lower triangle) on the device, from the CSR value arrays pk_csr fills (pk_extras.cpp).
+// Model-independent, so the two kernels live in the library like the shim's copy kernel, not in the generated code object.
+//
+// An operator is a CSR structure (indptr, indices) whose entry e takes its value from vals[src[e]] (src NULL: vals[e]): J^T
+// and the mirrored half of H point into the values of the map they were built from (pockit_amd/csr.py), nothing is copied or
+// transposed per iterate.  Its rows are cut ONCE, on the host, into work items of one 256-thread workgroup (pk_op_row_blocks):
+//
+//   stream block  consecutive whole rows with at most 256 entries (and 256 rows) together: one entry per thread, the products
+//                 meet in LDS, thread r adds the products of row r in ascending entry order
+//   piece block   256 consecutive entries of a row with more than 256 of them (the column of t_f in J^T): a fixed tree over
+//                 the 256 LDS slots leaves one partial sum; pk_op_long, one workgroup per long row, adds a row's partial sums
+//
+// Every y[row] is a fixed expression of the inputs: no atomics, no dependence on the grid, the same bits from run to run.
+#include "pk_runtime.h"
+
+// ---------------------------------------------------------------- row blocks (host, once per operator)
+int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBlock>& blocks, std::vector<PkOpLong>& longs,
+                     int32_t& n_slots) {
+  blocks.clear();
+  longs.clear();
+  int64_t slots = 0;
+  for (int32_t r = 0; r < n_rows;) {
+    const int32_t e0 = indptr[r], len = indptr[r + 1] - e0;
+    if (len > PK_BLOCK) {
+      const int32_t pieces = (len + PK_BLOCK - 1) / PK_BLOCK;
+      if (slots + pieces > INT32_MAX) return 1;
+      longs.push_back({r, (int32_t)slots, pieces});
+      for (int32_t p = 0; p < pieces; ++p)
+        blocks.push_back({e0 + p * PK_BLOCK, std::min<int32_t>(PK_BLOCK, len - p * PK_BLOCK), (int32_t)slots + p, -1});
+      slots += pieces;
+      ++r;
+    } else {
+      const int32_t r0 = r;
+      while (r < n_rows && r - r0 < PK_BLOCK && indptr[r + 1] - indptr[r] <= PK_BLOCK && indptr[r + 1] - e0 <= PK_BLOCK) ++r;
+      blocks.push_back({e0, indptr[r] - e0, r0, r - r0});
+    }
+    if (blocks.size() > (size_t)INT32_MAX) return 1;
+  }
+  n_slots = (int32_t)slots;
+  return 0;
+}
+
+// ---------------------------------------------------------------- the walk of one block, shared by the kernels and the host stand-in
+#ifdef __HIPCC__
+#define PK_OP_FN __host__ __device__ __forceinline__
+#else
+#define PK_OP_FN inline
+#endif
+
+// LDS slot of product i: one slot of padding behind every 32.  ds_read_b64 serves a wave as two halves of 32 lanes over
+// 64 banks of 4 bytes, i.e. 32 doubles per cycle: lane r of the row sums reads slot (start of row r) + k, a stride of the
+// row length -- 2, 4, 8 ... doubles for rows of equal even length would be 2-, 4-, 8-way conflicts; with the padding lanes
+// r and r + 32 / len land one bank pair further and the half-wave is conflict-free for every power-of-two length up to 32.
+#define PK_OP_LDS (PK_BLOCK + PK_BLOCK / 32)
+static_assert((PK_BLOCK & (PK_BLOCK - 1)) == 0, "the tree of pk_op_rows halves the workgroup");
+PK_OP_FN int op_slot(int i) { return i + (i >> 5); }
+
+struct PkOpArgs {
+  const PkOpBlock* blocks;
+  const PkOpLong* longs;
+  const int32_t *indptr, *indices, *src;
+  const double *vals, *v, *add;      // add may be NULL, and may alias y
+  double *y, *partial;
+  int32_t n_blocks, n_longs;
+};
+
+// thread t of a block: its product (0 beyond the block's count)
+PK_OP_FN double op_product(const PkOpArgs& a, const PkOpBlock& b, int t) {
+  if (t >= b.count) return 0.0;
+  const int32_t e = b.e0 + t;
+  return a.vals[a.src ? a.src[e] : e] * a.v[a.indices[e]];
+}
+
+// thread r < n_rows of a stream block: the products of its row in ascending entry order
+PK_OP_FN void op_row_sum(const PkOpArgs& a, const PkOpBlock& b, int r, const double* s) {
+  const int32_t row = b.row0 + r;
+  const int lo = a.indptr[row] - b.e0, hi = a.indptr[row + 1] - b.e0;
+  double sum = 0.0;
+  for (int k = lo; k < hi; ++k) sum += s[op_slot(k)];
+  a.y[row] = a.add ? sum + a.add[row] : sum;
+}
+
+// thread t of a long row: its partial sums first + t, first + t + 256, ... in ascending order
+PK_OP_FN double op_long_strided(const PkOpArgs& a, const PkOpLong& l, int t) {
+  double sum = 0.0;
+  for (int32_t k = t; k < l.pieces; k += PK_BLOCK) sum += a.partial[l.first + k];
+  return sum;
+}
+
+// one step of the fixed tree over the 256 slots: widths 128, 64 ... 1
+PK_OP_FN void op_tree_step(double* s, int w, int t) {
+  if (t < w) s[op_slot(t)] += s[op_slot(t + w)];
+}
+
+#ifdef __HIPCC__
+// ---------------------------------------------------------------- kernels (gfx950)
+__device__ __forceinline__ double op_tree(double* s, int t) {      // (every thread of the workgroup; returns the sum to all)
+  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1) {
+    op_tree_step(s, w, t);
+    __syncthreads();
+  }
+  return s[0];
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_op_rows(PkOpArgs a) {
+  __shared__ double s[PK_OP_LDS];
+  const int t = (int)threadIdx.x;
+  for (int32_t i = (int32_t)blockIdx.x; i < a.n_blocks; i += (int32_t)gridDim.x) {
+    const PkOpBlock b = a.blocks[i];
+    s[op_slot(t)] = op_product(a, b, t);
+    __syncthreads();
+    if (b.n_rows >= 0) {      // (uniform over the workgroup)
+      if (t < b.n_rows) op_row_sum(a, b, t, s);
+    } else {
+      const double sum = op_tree(s, t);
+      if (t == 0) a.partial[b.row0] = sum;
+    }
+    __syncthreads();          // the next block of this workgroup's stride overwrites the slots
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_op_long(PkOpArgs a) {
+  __shared__ double s[PK_OP_LDS];
+  const int t = (int)threadIdx.x;
+  for (int32_t i = (int32_t)blockIdx.x; i < a.n_longs; i += (int32_t)gridDim.x) {
+    const PkOpLong l = a.longs[i];
+    s[op_slot(t)] = op_long_strided(a, l, t);
+    __syncthreads();
+    const double sum = op_tree(s, t);
+    if (t == 0) a.y[l.row] = a.add ? sum + a.add[l.row] : sum;
+    __syncthreads();
+  }
+}
+#else
+// ---------------------------------------------------------------- host stand-in: the identical walk over the same tables
+static void op_tree_host(double* s) {
+  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1)
+    for (int t = 0; t < PK_BLOCK; ++t) op_tree_step(s, w, t);
+}
+
+static void op_rows_host(const PkOpArgs& a, unsigned grid) {
+  double s[PK_OP_LDS];
+  for (unsigned wg = 0; wg < grid; ++wg)
+    for (int32_t i = (int32_t)wg; i < a.n_blocks; i += (int32_t)grid) {
+      const PkOpBlock b = a.blocks[i];
+      for (int t = 0; t < PK_BLOCK; ++t) s[op_slot(t)] = op_product(a, b, t);
+      if (b.n_rows >= 0) {
+        for (int t = 0; t < b.n_rows; ++t) op_row_sum(a, b, t, s);
+      } else {
+        op_tree_host(s);
+        a.partial[b.row0] = s[0];
+      }
+    }
+}
+
+static void op_long_host(const PkOpArgs& a, unsigned grid) {
+  double s[PK_OP_LDS];
+  for (unsigned wg = 0; wg < grid; ++wg)
+    for (int32_t i = (int32_t)wg; i < a.n_longs; i += (int32_t)grid) {
+      const PkOpLong l = a.longs[i];
+      for (int t = 0; t < PK_BLOCK; ++t) s[op_slot(t)] = op_long_strided(a, l, t);
+      op_tree_host(s);
+      a.y[l.row] = a.add ? s[0] + a.add[l.row] : s[0];
+    }
+}
+#endif
+
+// The grid rule of both kernels, stated once: one workgroup per work item up to PK_OP_GRID_CAP (8 workgroups of 256 threads
+// fill a CU's 2048 thread slots, 256 CUs), the items beyond it in a stride loop -- the result does not depend on it.
+enum { PK_OP_GRID_CAP = 2048 };
+static unsigned op_grid(int32_t items) { return (unsigned)std::min<int32_t>(items, PK_OP_GRID_CAP); }
+
+static void free_operator(PkOperator& o) {
+  release(o.d_indptr); release(o.d_indices); release(o.d_src); release(o.d_blocks); release(o.d_longs); release(o.d_partial);
+  o = PkOperator{};
+}
+
+void free_operators(pk_ctx* c) {
+  for (auto& o : c->ops.op) free_operator(o);
+  release(c->ops.d_v); release(c->ops.d_y);
+  c->ops.lin_J = c->ops.lin_H = nullptr;
+}
+
+void drop_linearization(pk_ctx* c) { c->ops.lin_J = c->ops.lin_H = nullptr; }
+
+extern "C" {
+
+int pk_set_csr_operator(pk_ctx* c, int op, const int32_t* indptr, const int32_t* indices, const int32_t* src, int32_t n_rows,
+                        int32_t n_cols, int64_t nnz) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (op < 0 || op > 2) return fail(c, 110, "pk_set_csr_operator: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  if (!indptr || !indices) return fail(c, 110, "pk_set_csr_operator: null structure");
+  if (c->shard.flags || c->exchange.world > 1) return fail(c, 119, "pk_set_csr_operator: not offered for a sharded context");
+  const int64_t n_unique = c->csr[op == 2 ? 1 : 0].n_unique;
+  if (n_unique == 0)
+    return fail(c, 111, "pk_set_csr_operator: call pk_set_csr_map(%d) first (the operator takes its values from that map's CSR array)", op == 2 ? 1 : 0);
+  const int32_t want_rows = op == 0 ? c->m : c->n, want_cols = op == 1 ? c->m : c->n;
+  if (n_rows != want_rows || n_cols != want_cols || nnz <= 0 || (!src && nnz != n_unique))
+    return fail(c, 112, "pk_set_csr_operator: %d x %d with %lld entries does not match the problem (%d x %d%s)", n_rows, n_cols,
+                (long long)nnz, want_rows, want_cols, src ? "" : ", one entry per CSR value without src");
+  if (nnz > INT32_MAX) return fail(c, 116, "pk_set_csr_operator: %lld entries do not fit 32-bit indices", (long long)nnz);
+  // validate on the host everything a kernel indexes with
+  if (indptr[0] != 0 || indptr[n_rows] != nnz) return fail(c, 113, "pk_set_csr_operator: indptr does not cover the entries");
+  for (int32_t r = 0; r < n_rows; ++r)
+    if (indptr[r + 1] < indptr[r]) return fail(c, 113, "pk_set_csr_operator: indptr decreases at row %d", r);
+  for (int64_t e = 0; e < nnz; ++e)
+    if (indices[e] < 0 || indices[e] >= n_cols) return fail(c, 114, "pk_set_csr_operator: indices[%lld] out of range", (long long)e);
+  if (src)
+    for (int64_t e = 0; e < nnz; ++e)
+      if (src[e] < 0 || src[e] >= n_unique) return fail(c, 115, "pk_set_csr_operator: src[%lld] out of range", (long long)e);
+  std::vector<PkOpBlock> blocks;
+  std::vector<PkOpLong> longs;
+  int32_t n_slots = 0;
+  if (pk_op_row_blocks(indptr, n_rows, blocks, longs, n_slots))
+    return fail(c, 116, "pk_set_csr_operator: the row blocks do not fit 32-bit counts");
+  PK_HIP(c, hipSetDevice(c->device));
+  PK_HIP(c, hipStreamSynchronize(c->stream));
+  PkOperator& o = c->ops.op[op];
+  free_operator(o);
+  if ((rc = upload(c, (void**)&o.d_indptr, indptr, sizeof(int32_t) * ((size_t)n_rows + 1)))) return rc;
+  if ((rc = upload(c, (void**)&o.d_indices, indices, sizeof(int32_t) * (size_t)nnz))) return rc;
+  if (src && (rc = upload(c, (void**)&o.d_src, src, sizeof(int32_t) * (size_t)nnz))) return rc;
+  if ((rc = upload(c, (void**)&o.d_blocks, blocks.data(), sizeof(PkOpBlock) * blocks.size()))) return rc;
+  if (!longs.empty()) {
+    if ((rc = upload(c, (void**)&o.d_longs, longs.data(), sizeof(PkOpLong) * longs.size()))) return rc;
+    PK_HIP(c, hipMalloc((void**)&o.d_partial, sizeof(double) * (size_t)n_slots));
+  }
+  if (!c->ops.d_v) {      // scratch vectors of the host form (pk_apply_operator): every operator's v and y fit
+    const size_t len = (size_t)std::max(c->n, c->m);
+    PK_HIP(c, hipMalloc((void**)&c->ops.d_v, sizeof(double) * len));
+    PK_HIP(c, hipMalloc((void**)&c->ops.d_y, sizeof(double) * len));
+  }
+  o.n_rows = n_rows; o.n_cols = n_cols; o.nnz = nnz;
+  o.n_blocks = (int32_t)blocks.size(); o.n_longs = (int32_t)longs.size();
+  return 0;
+}
+
+int pk_apply_operator_dev(pk_ctx* c, int op, const double* d_vals, const double* d_v, const double* d_add, double* d_y,
+                          void* stream) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  const PkOperator& o = c->ops.op[op];
+  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator: call pk_set_csr_operator(%d) first", op);
+  if (!d_vals || !d_v || !d_y) return fail(c, 110, "pk_apply_operator: null device pointer");
+  PkOpArgs a{};
+  a.blocks = o.d_blocks; a.longs = o.d_longs; a.indptr = o.d_indptr; a.indices = o.d_indices; a.src = o.d_src;
+  a.vals = d_vals; a.v = d_v; a.add = d_add; a.y = d_y; a.partial = o.d_partial;
+  a.n_blocks = o.n_blocks; a.n_longs = o.n_longs;
+  hipStream_t st = pick(c, stream);
+  const unsigned grid = op_grid(o.n_blocks), grid_long = op_grid(o.n_longs);
+#ifdef __HIPCC__
+  hipLaunchKernelGGL(pk_op_rows, dim3(grid), dim3(PK_BLOCK), 0, st, a);
+  PK_HIP(c, hipGetLastError());
+  if (grid_long) {
+    hipLaunchKernelGGL(pk_op_long, dim3(grid_long), dim3(PK_BLOCK), 0, st, a);
+    PK_HIP(c, hipGetLastError());
+  }
+#else
+  fake_hip_enqueue(st, [a, grid]() { op_rows_host(a, grid); });
+  if (grid_long) fake_hip_enqueue(st, [a, grid_long]() { op_long_host(a, grid_long); });
+#endif
+  return 0;
+}
+
+int pk_linearize(pk_ctx* c, const double* x, const double* lambda, double sigma) {
+  if (const int rc = host_ready(c, x != nullptr)) return rc;
+  const PkCsrMap& mj = c->csr[c->csr[3].n_unique > 0 ? 3 : 0];      // (the value arrays pk_eval_jac_csr / pk_eval_hess_csr choose)
+  const PkCsrMap& mh = c->csr[c->csr[2].n_unique > 0 ? 2 : 1];
+  if (mj.n_unique == 0 || (lambda && mh.n_unique == 0))
+    return fail(c, 111, "pk_linearize: call pk_set_csr_map first (0%s)", lambda ? " and 1" : "");
+  drop_linearization(c);
+  const int rc = host_eval(c, x, lambda, {}, false, [&] {
+    const int rj = pk_eval_jac_csr_dev(c, c->d_x, mj.d_vals, nullptr);
+    return rj || !lambda ? rj : pk_eval_hess_csr_dev(c, c->d_x, c->d_lam, sigma, mh.d_vals, nullptr);
+  });
+  if (rc) return rc;
+  c->ops.lin_J = mj.d_vals;
+  c->ops.lin_H = lambda ? mh.d_vals : nullptr;
+  return 0;
+}
+
+int pk_apply_operator(pk_ctx* c, int op, const double* v, double* y) {
+  if (const int rc = host_ready(c, v && y)) return rc;
+  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  const PkOperator& o = c->ops.op[op];
+  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator: call pk_set_csr_operator(%d) first", op);
+  const double* vals = op == 2 ? c->ops.lin_H : c->ops.lin_J;
+  if (!vals && op == 2 && c->ops.lin_J) return fail(c, 118, "pk_apply_operator: the linearization has no Hessian (pk_linearize without lambda)");
+  if (!vals) return fail(c, 118, "pk_apply_operator: no linearization (pk_linearize)");
+  PK_HIP(c, hipSetDevice(c->device));
+  PK_HIP(c, hipMemcpyAsync(c->ops.d_v, v, sizeof(double) * (size_t)o.n_cols, hipMemcpyHostToDevice, c->stream));
+  if (const int rc = pk_apply_operator_dev(c, op, vals, c->ops.d_v, nullptr, c->ops.d_y, nullptr)) return rc;
+  PK_HIP(c, hipMemcpyAsync(y, c->ops.d_y, sizeof(double) * (size_t)o.n_rows, hipMemcpyDeviceToHost, c->stream));
+  PK_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+}  // extern "C"

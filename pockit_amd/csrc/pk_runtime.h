@@ -6,6 +6,7 @@
 //   pk_shard.cpp    sharding: shard flags, peer / IPC / registered memory, the exchange of the partial sums, run copies
 //   pk_batch.cpp    a batch of iterates in one launch of the fused cycle (pk_cycleb): batched object, per-entry workspaces
 //   pk_extras.cpp   CSR hand-off, mesh error estimation, profiling and developer tracing
+//   pk_ops.cpp      J, J^T and the symmetric H applied to vectors on the device (pk_op_rows, pk_op_long: the library's own kernels)
 //   pk_error.cpp    fail(): where an error message is kept
 //
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
@@ -113,6 +114,29 @@ struct PkCsrMap {
   int32_t *d_seg = nullptr, *d_perm = nullptr;
   double* d_vals = nullptr;
   int64_t n_unique = 0, n_triplets = 0;
+};
+
+// ---- operators over the CSR values (pk_set_csr_operator; pk_ops.cpp: free_operators)
+// A work item of one workgroup of pk_op_rows.  n_rows >= 0: a stream block, the whole rows [row0, row0 + n_rows) = the entries
+// [e0, e0 + count); n_rows = -1: a piece block, count consecutive entries of a long row, row0 = its slot in the partial sums.
+struct PkOpBlock {
+  int32_t e0, count, row0, n_rows;
+};
+struct PkOpLong {      // a row with more than PK_BLOCK entries: its partial sums are the slots [first, first + pieces)
+  int32_t row, first, pieces;
+};
+struct PkOperator {
+  int32_t *d_indptr = nullptr, *d_indices = nullptr, *d_src = nullptr;   // d_src NULL: entry e takes vals[e]
+  PkOpBlock* d_blocks = nullptr;
+  PkOpLong* d_longs = nullptr;
+  double* d_partial = nullptr;
+  int32_t n_rows = 0, n_cols = 0, n_blocks = 0, n_longs = 0;             // n_blocks = 0: not set
+  int64_t nnz = 0;
+};
+struct PkOps {
+  PkOperator op[3];                          // 0 J, 1 J^T, 2 H symmetric
+  double *d_v = nullptr, *d_y = nullptr;     // scratch vectors of pk_apply_operator, max(n, m) doubles each
+  const double *lin_J = nullptr, *lin_H = nullptr;   // the linearization of pk_linearize: CSR value arrays of the maps (NULL: none)
 };
 
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
@@ -263,6 +287,7 @@ struct pk_ctx : pk_error_state {
   PkCsrMap csr[4];   // [0] Jacobian, [1] Hessian of the Lagrangian (lower triangle)
                      // + [2]: compact Hessian values -> the same CSR entries (a pure permutation: one value per entry)
                      // + [3]: compact Jacobian values -> the CSR entries of J (the few repeated positions summed)
+  PkOps ops;
   PkMeshError mesh_error;
   PkShim shim;
 };
@@ -337,6 +362,15 @@ void unload_batch_model(pk_ctx* c); // the batched code object (with the model)
 void free_csr(pk_ctx* c);
 void free_mesh_error(pk_ctx* c);
 void free_trace(pk_ctx* c);
+
+// ---- pk_ops.cpp
+void free_operators(pk_ctx* c);      // with the problem, and with every pk_set_csr_map: an operator's src refers to a map
+void drop_linearization(pk_ctx* c);  // the CSR value arrays of the maps are about to hold something else
+// The rows of a CSR structure (indptr validated: monotone from 0) cut in order into the work items of pk_op_rows: stream blocks
+// of whole rows (empty ones included) with at most PK_BLOCK entries and PK_BLOCK rows, ceil(len / PK_BLOCK) piece blocks for a
+// row with more than PK_BLOCK entries, and the list of those long rows.  Pure; nonzero: a count does not fit 32 bits.
+int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBlock>& blocks, std::vector<PkOpLong>& longs,
+                     int32_t& n_slots);
 
 // ---- the host-buffer form of an entry point: upload x (and lambda), the device-pointer entry point, download, synchronize
 inline int host_ready(pk_ctx* c, bool buffers) {

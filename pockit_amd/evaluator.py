@@ -447,6 +447,8 @@ class Evaluator:
         md = model_desc(self.src)
         self._err_views = None
         self._csr = {}
+        self._ops = {}               # operators uploaded to the context (pk_set_csr_operator): "J", "JT", "H"
+        self._lin_gen = 0            # generation of the context's ONE linearization (Linearization handles compare with it)
         self._code = code
         self._views = {}
         self.zero_copy = False   # True: callbacks return views of pinned buffers (set by the IPOPT adapter)
@@ -463,6 +465,8 @@ class Evaluator:
         plan, lib, h = self.plan, self.ctx.lib, self.ctx.handle
         self.tables = tb
         self._views = {}
+        self._csr, self._ops = {}, {}      # (pk_set_problem frees the maps and the operators of the context)
+        self._lin_gen += 1
         pd = runtime.ProblemDesc()
         pd.n, pd.m, pd.n_sys, pd.n_s, pd.l_s = plan.n, plan.m, plan.n_sys, plan.n_s, plan.l_s
         pd.n_phase, pd.n_tiles, pd.n_kinds = len(tb.phases), len(tb.tiles), len(tb.kinds)
@@ -608,6 +612,7 @@ class Evaluator:
 
     def _invalidate_x(self):
         """The context's x / result buffers are about to be used by an entry point outside the prepared-x protocol."""
+        self._lin_gen += 1      # (... and a Linearization handed out before is stale)
         if self.ctx is not None:
             self.ctx.lib.pk_invalidate_x(self.ctx.handle)
 
@@ -793,6 +798,8 @@ class Evaluator:
             else:
                 m = CsrMap(plan.hess_row, plan.hess_col, (plan.n, plan.n))
             seg = None if m.seg is None else m.seg.ctypes.data_as(runtime.c_int32_p)
+            self._ops = {}          # pk_set_csr_map drops the context's operators and its linearization
+            self._lin_gen += 1
             self.ctx.check(self.ctx.lib.pk_set_csr_map(self.ctx.handle, 0 if which == "jac" else 1, seg,
                                                        m.perm.ctypes.data_as(runtime.c_int32_p), m.nnz, m.n_triplets))
             self._csr[which] = m
@@ -852,6 +859,50 @@ class Evaluator:
         self.csr_map(which)
         self.ctx.check(self.ctx.lib.pk_gather_csr_dev(self.ctx.handle, 0 if which == "jac" else 1, d_triplets, d_out,
                                                       stream))
+
+    # ------------------------------------------------------------------ J, J^T and H applied to vectors on the device
+    OPERATORS = {"J": 0, "JT": 1, "H": 2}
+
+    def _operator(self, op):
+        """Number of the operator ``op`` for the C ABI; its structure (csr.CsrOperator, from the maps) is built and uploaded
+        on first use, like ``csr_map``."""
+        if op not in self.OPERATORS:
+            raise ValueError('op must be "J", "JT" or "H"')
+        if self.src.sharded:
+            raise NotImplementedError("the device-side operators are not offered for a sharded evaluator")
+        m = self.csr_map("hess" if op == "H" else "jac")      # (first: a new map drops the operators)
+        if op not in self._ops:
+            o = m.operator() if op == "J" else m.transposed() if op == "JT" else m.symmetric()
+            i32 = lambda a: None if a is None else a.ctypes.data_as(runtime.c_int32_p)  # noqa: E731
+            self.ctx.check(self.ctx.lib.pk_set_csr_operator(self.ctx.handle, self.OPERATORS[op], i32(o.indptr), i32(o.indices),
+                                                            i32(o.src), o.shape[0], o.shape[1], o.nnz))
+            self._ops[op] = o
+        return self.OPERATORS[op]
+
+    def apply_operator_dev(self, op, d_vals, d_v, d_y, d_add=None, stream=None):
+        """``y = A(vals) v (+ add)`` on device pointers, ``op`` one of "J", "JT", "H"; ``d_vals``: a CSR value array as
+        ``jacobian_csr_dev`` / ``hessian_csr_dev`` / ``gather_csr_dev`` fill it.  ``d_add`` may alias ``d_y``.  Enqueued on
+        ``stream``, not waited for."""
+        k = self._operator(op)
+        self.ctx.check(self.ctx.lib.pk_apply_operator_dev(self.ctx.handle, k, d_vals, d_v, d_add, d_y, stream))
+
+    def linearize(self, x, lagrange=None, obj_factor=1.0):
+        """Evaluate J at ``x`` -- and the Hessian of the Lagrangian with ``(lagrange, obj_factor)`` unless ``lagrange`` is
+        None -- into the context's CSR value arrays and leave them on the device: the ``Linearization`` returned multiplies
+        with them, one vector each way per product.  A context holds ONE linearization: the handle is stale after the next
+        ``linearize`` and after any call that gives the context's buffers another evaluation (``jacobian_csr``, ``cycle``, the
+        ``*_direct`` and ``*_dev`` entry points ...); the callbacks of the prepared-x protocol leave it alone."""
+        x = self._x(x)
+        lam = None if lagrange is None else self._lam(lagrange)
+        self.csr_map("jac")         # (both maps before any operator: a new map drops the operators)
+        if lam is not None:
+            self.csr_map("hess")
+        for op in ("J", "JT") + (("H",) if lam is not None else ()):
+            self._operator(op)
+        self._invalidate_x()        # the context's x buffer is about to hold another iterate; earlier handles are stale
+        self.ctx.check(self.ctx.lib.pk_linearize(self.ctx.handle, runtime.as_dp(x), None if lam is None else runtime.as_dp(lam),
+                                                 float(obj_factor)))
+        return Linearization(self, self._lin_gen, lam is not None)
 
     def cycle(self, x, lagrange, obj_factor):
         """All five outputs on the same x from ONE call and ONE launch (pk_cycle): returns (f, grad, g, J, H).  Staging and
@@ -1110,3 +1161,48 @@ class Evaluator:
             self.ctx.check(self.ctx.lib.pk_profile_read(self.ctx.handle, k, C.byref(n), C.byref(ms)))
             out[name] = (n.value, ms.value)
         return out
+
+
+class Linearization:
+    """J (and H) of one iterate, resident on the device (``Evaluator.linearize``): products with host vectors."""
+
+    def __init__(self, evaluator, generation, has_hessian):
+        self._ev, self._gen, self.has_hessian = evaluator, generation, has_hessian
+        self.m, self.n = evaluator.plan.m, evaluator.plan.n
+
+    def _apply(self, op, v, n_in, n_out):
+        ev = self._ev
+        if ev.ctx is None or self._gen != ev._lin_gen:
+            raise RuntimeError("stale linearization: the evaluator has been given another evaluation since (one linearization per context)")
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (n_in,):
+            raise ValueError(f"the vector must have shape ({n_in},)")
+        y = np.empty(n_out)
+        ev.ctx.check(ev.ctx.lib.pk_apply_operator(ev.ctx.handle, ev.OPERATORS[op], runtime.as_dp(v), runtime.as_dp(y)))
+        return y
+
+    def jv(self, v):
+        """``J v``"""
+        return self._apply("J", v, self.n, self.m)
+
+    def jtv(self, y):
+        """``J^T y``"""
+        return self._apply("JT", y, self.m, self.n)
+
+    def hv(self, v):
+        """``H v`` with the full symmetric Hessian of the Lagrangian"""
+        if not self.has_hessian:
+            raise RuntimeError("this linearization has no Hessian: linearize(x, lagrange, obj_factor)")
+        return self._apply("H", v, self.n, self.n)
+
+    def jacobian_operator(self):
+        from scipy.sparse.linalg import LinearOperator
+
+        flat = lambda f: lambda v: f(np.asarray(v).reshape(-1))  # noqa: E731  (SciPy also passes columns)
+        return LinearOperator((self.m, self.n), matvec=flat(self.jv), rmatvec=flat(self.jtv), dtype=np.float64)
+
+    def hessian_operator(self):
+        from scipy.sparse.linalg import LinearOperator
+
+        hv = lambda v: self.hv(np.asarray(v).reshape(-1))  # noqa: E731
+        return LinearOperator((self.n, self.n), matvec=hv, rmatvec=hv, dtype=np.float64)

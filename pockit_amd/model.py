@@ -710,6 +710,12 @@ class SystemBase:
         ev = self.evaluator
         return ev.csr_map("hess").to_scipy(ev.hessian_csr(x, lagrange, obj_factor))
 
+    def linearize(self, x, lagrange=None, obj_factor=1.0):
+        """J (and, with ``lagrange``, the Hessian of the Lagrangian) of the iterate kept on the GPU: the ``Linearization``
+        returned has ``jv``, ``jtv``, ``hv`` and the two as ``scipy.sparse.linalg.LinearOperator`` -- a product moves one
+        vector each way instead of the matrix (``Evaluator.linearize``)."""
+        return self.evaluator.linearize(x, lagrange, obj_factor)
+
     # ------------------------------------------------------------------ mesh error check / refinement
     # (reference: systembase.py:837-889 check_continuous, 982-1069 refine_continuous)
     def _split_value(self, value):

@@ -97,6 +97,10 @@ PROTOTYPES = {
     "pk_eval_hess_csr_dev": (C.c_int, [vp, vp, vp, C.c_double, vp, vp]),
     "pk_eval_jac_csr": (C.c_int, [vp, dp, dp]),
     "pk_eval_hess_csr": (C.c_int, [vp, dp, dp, C.c_double, dp]),
+    "pk_set_csr_operator": (C.c_int, [vp, C.c_int, c_int32_p, c_int32_p, c_int32_p, C.c_int32, C.c_int32, C.c_int64]),
+    "pk_apply_operator_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    "pk_linearize": (C.c_int, [vp, dp, dp, C.c_double]),
+    "pk_apply_operator": (C.c_int, [vp, C.c_int, dp, dp]),
     "pk_eval_f_dev": (C.c_int, [vp, vp, vp, vp]),
     "pk_eval_grad_dev": (C.c_int, [vp, vp, vp, vp]),
     "pk_eval_g_dev": (C.c_int, [vp, vp, vp, vp]),
