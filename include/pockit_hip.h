@@ -200,8 +200,9 @@ int pk_eval_hess_csr(pk_ctx* ctx, const double* x, const double* lambda, double 
  * array of a map (src NULL: vals[e]): pockit_amd/csr.py builds the three from the maps (J itself; the transpose; L + L^T -
  * diag(L), each off-diagonal entry twice with one src).  pk_set_csr_operator needs the matching pk_set_csr_map (which = 0 for
  * op 0 / 1, which = 1 for op 2), checks everything a kernel will index with (errors 110-116, 119) and cuts the rows into
- * the kernels' work items; pk_set_csr_map and pk_set_problem drop every operator.  Every y[row] is a fixed expression of the
- * inputs (no atomics): the same bits from run to run.  ``d_add`` may be NULL and may alias ``d_y``.
+ * the kernels' work items; pk_set_csr_map and pk_set_problem drop every operator.  indices and src are only range-checked: a
+ * row may list a column more than once, in any order, and y[row] is then the sum over the listed entries.  Every y[row] is
+ * a fixed expression of the inputs (no atomics): the same bits from run to run.  ``d_add`` may be NULL and may alias ``d_y``.
  * pk_linearize evaluates the CSR values of J at x -- and of H with (lambda, sigma) unless lambda is NULL -- into the
  * context's own value arrays (the ones pk_eval_jac_csr / pk_eval_hess_csr use) and downloads nothing; pk_apply_operator
  * sends v up, multiplies with that linearization and brings y down (error 118: no linearization, or none of H for op 2;
