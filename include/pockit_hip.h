@@ -1,6 +1,6 @@
 /* pockit_hip.h -- C ABI of the MI355X NLP-callback evaluator (libpockit_hip.so).
  *
- * STABLE SURFACE.  The 42 entry points declared here are the contract of the library: what a second host binding for
+ * STABLE SURFACE.  The 44 entry points declared here are the contract of the library: what a second host binding for
  * pockit's evaluator path needs -- life cycle, evaluation on host buffers and on device pointers, the compact layouts, the CSR
  * hand-off and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
  * shim, the sharding transport, the helper threads, tuning switches and diagnostics) is declared in
@@ -213,6 +213,18 @@ int pk_apply_operator_dev(pk_ctx* ctx, int op, const double* d_vals, const doubl
                           void* stream);
 int pk_linearize(pk_ctx* ctx, const double* x, const double* lambda /* or NULL */, double sigma);
 int pk_apply_operator(pk_ctx* ctx, int op, const double* v, double* y);
+/* The same operators applied to a BLOCK of k >= 1 vectors in one call: Y = A V (+ Add).  Device layout row-major with leading
+ * dimensions: V[i * ldv + j] (row i < n_cols, column j < k, ldv >= k), Y[r * ldy + j] (ldy >= k), Add NULL or laid out like Y
+ * with the same ldy, and it may alias Y -- NumPy's C order for an (n, k) array when ld = k; ld > k addresses a column range of
+ * a wider block in place.  Only entries of Y with a column index below k are written.  A workgroup handles up to 8 columns of
+ * one row block and reads the structure and the values once for them; k > 8 runs ceil(k / 8) chunks of launches on the stream.
+ * Column j of Y has exactly the bits pk_apply_operator_dev gives for column j of V (and of Add).  Errors as for the single
+ * form (110, 117, 118), and 120: k < 1; 121: ldv < k or ldy < k; 122: no device memory for the block's partial sums (allocated
+ * on an operator's first block product) or for the host form's scratch (grown to max(n, m) * k doubles when k exceeds what it
+ * holds).  The host form takes C-contiguous V (n_cols x k) and Y (n_rows x k) and multiplies with the context's linearization. */
+int pk_apply_operator_block_dev(pk_ctx* ctx, int op, const double* d_vals, int32_t k, const double* d_V, int64_t ldv,
+                                const double* d_Add, double* d_Y, int64_t ldy, void* stream);
+int pk_apply_operator_block(pk_ctx* ctx, int op, int32_t k, const double* V, double* Y);
 
 /* device-pointer API: enqueue on ``stream`` (hipStream_t, NULL = context stream), no sync */
 int pk_eval_f_dev(pk_ctx* ctx, const double* d_x, double* d_f, void* stream);

@@ -12,6 +12,11 @@
 //                 the 256 LDS slots leaves one partial sum; pk_op_long, one workgroup per long row, adds a row's partial sums
 //
 // Every y[row] is a fixed expression of the inputs: no atomics, no dependence on the grid, the same bits from run to run.
+//
+// A BLOCK of k vectors (pk_apply_operator_block[_dev]: Y = A V (+ Add), V and Y row-major with leading dimensions) walks the
+// same row blocks in chunks of at most PK_OP_KMAX columns: pk_op_rows_k / pk_op_long_k read the structure and the values once
+// per chunk and keep one LDS plane of products per column.  Column j of Y has exactly the bits of the single product with
+// column j of V: the association per (row, column) is the one above.
 #include "pk_runtime.h"
 
 // ---------------------------------------------------------------- row blocks (host, once per operator)
@@ -93,6 +98,95 @@ PK_OP_FN void op_tree_step(double* s, int w, int t) {
   if (t < w) s[op_slot(t)] += s[op_slot(t + w)];
 }
 
+// ---------------------------------------------------------------- the same walk for a chunk of kc <= PK_OP_KMAX columns
+// One LDS plane of PK_OP_LDS slots per column, the planes behind one another: product (i, c) lies at c * PK_OP_LDS + op_slot(i).
+// The lanes of a half-wave work on consecutive i of ONE plane wherever the workgroup is full (the stores of the products, the
+// row sums of a block with 32 rows or more, the wide levels of the tree), so the bank reasoning of op_slot carries over plane
+// by plane; a plane's 264 doubles shift the next one by 8 doubles = 16 banks, which matters only where a half-wave crosses
+// planes (blocks of fewer than 32 rows, tree levels below 32).  Not measured.
+struct PkOpArgsK {
+  PkOpArgs a;            // v, add and y point at the chunk's first column; partial holds PK_OP_KMAX doubles per slot
+  int64_t ldv, ldy;      // doubles between two rows of V, and of Y and Add
+  int32_t kc;            // columns of this chunk
+};
+
+// two doubles from a 16-byte aligned address: one 16-byte load
+PK_OP_FN void op_load_pair(const double* p, double& x, double& y) {
+  double q[2];
+  __builtin_memcpy(q, __builtin_assume_aligned(p, 16), sizeof q);
+  x = q[0];
+  y = q[1];
+}
+
+// thread t of a block: its kc products into the planes (0 beyond the block's count); value, column and src are read once
+PK_OP_FN void op_products_k(const PkOpArgsK& k, const PkOpBlock& b, int t, double* s) {
+  const PkOpArgs& a = k.a;
+  double* p = s + op_slot(t);
+  if (t >= b.count) {
+    for (int c = 0; c < k.kc; ++c) p[c * PK_OP_LDS] = 0.0;
+    return;
+  }
+  const int32_t e = b.e0 + t;
+  const double val = a.vals[a.src ? a.src[e] : e];
+  const double* v = a.v + (int64_t)a.indices[e] * k.ldv;
+  int c = 0;
+  if (((((uintptr_t)a.v) | ((uintptr_t)k.ldv << 3)) & 15) == 0)      // (uniform over the launch) every row of the chunk is 16-byte aligned
+    for (; c + 1 < k.kc; c += 2) {
+      double x, y;
+      op_load_pair(v + c, x, y);
+      p[c * PK_OP_LDS] = val * x;
+      p[(c + 1) * PK_OP_LDS] = val * y;
+    }
+  for (; c < k.kc; ++c) p[c * PK_OP_LDS] = val * v[c];
+}
+
+// thread t of a stream block: the n_rows x kc sums are spread over the workgroup, PK_BLOCK / n_rows columns side by side --
+// thread q * n_rows + r takes row r in the columns q, q + PK_BLOCK / n_rows, ... -- each the products of its row in its plane
+// in ascending entry order.  Every (row, column) has one writer, which reads add first.
+PK_OP_FN void op_row_sums_k(const PkOpArgsK& k, const PkOpBlock& b, int t, const double* s) {
+  const PkOpArgs& a = k.a;
+  if (b.n_rows <= 0) return;
+  const int step = PK_BLOCK / b.n_rows, q = t / b.n_rows, r = t - q * b.n_rows;
+  if (q >= step) return;      // (the threads behind the last whole group of n_rows)
+  const int32_t row = b.row0 + r;
+  const int lo = a.indptr[row] - b.e0, hi = a.indptr[row + 1] - b.e0;
+  for (int c = q; c < k.kc; c += step) {
+    const double* p = s + c * PK_OP_LDS;
+    double sum = 0.0;
+    for (int i = lo; i < hi; ++i) sum += p[op_slot(i)];
+    const int64_t at = (int64_t)row * k.ldy + c;
+    a.y[at] = a.add ? sum + a.add[at] : sum;
+  }
+}
+
+// thread t of a long row: per column its partial sums first + t, first + t + 256, ... in ascending order
+PK_OP_FN void op_long_strided_k(const PkOpArgsK& k, const PkOpLong& l, int t, double* s) {
+  for (int c = 0; c < k.kc; ++c) {
+    double sum = 0.0;
+    for (int32_t j = t; j < l.pieces; j += PK_BLOCK) sum += k.a.partial[(int64_t)(l.first + j) * PK_OP_KMAX + c];
+    s[c * PK_OP_LDS + op_slot(t)] = sum;
+  }
+}
+
+// one step of the kc trees, which share the barrier of the level: the PK_BLOCK / w groups of w threads take a column each
+PK_OP_FN void op_tree_step_k(double* s, int w, int t, int kc) {
+  const int i = t & (w - 1);
+  for (int c = t / w; c < kc; c += PK_BLOCK / w) {
+    double* p = s + c * PK_OP_LDS;
+    p[op_slot(i)] += p[op_slot(i + w)];
+  }
+}
+
+// thread t < kc behind the trees: the sum of column t
+PK_OP_FN void op_store_partial_k(const PkOpArgsK& k, const PkOpBlock& b, int t, const double* s) {
+  k.a.partial[(int64_t)b.row0 * PK_OP_KMAX + t] = s[t * PK_OP_LDS];
+}
+PK_OP_FN void op_store_long_k(const PkOpArgsK& k, const PkOpLong& l, int t, const double* s) {
+  const int64_t at = (int64_t)l.row * k.ldy + t;
+  const double sum = s[t * PK_OP_LDS];
+  k.a.y[at] = k.a.add ? sum + k.a.add[at] : sum;
+}
+
 #ifdef __HIPCC__
 // ---------------------------------------------------------------- kernels (gfx950)
 __device__ __forceinline__ double op_tree(double* s, int t) {      // (every thread of the workgroup; returns the sum to all)
@@ -132,6 +226,43 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_op_long(PkOpArgs a) {
     __syncthreads();
   }
 }
+__device__ __forceinline__ void op_tree_k(double* s, int t, int kc) {      // (every thread of the workgroup; column c ends in s[c * PK_OP_LDS])
+#pragma unroll
+  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1) {
+    op_tree_step_k(s, w, t, kc);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_op_rows_k(PkOpArgsK k) {
+  __shared__ double s[PK_OP_KMAX * PK_OP_LDS];
+  const int t = (int)threadIdx.x;
+  for (int32_t i = (int32_t)blockIdx.x; i < k.a.n_blocks; i += (int32_t)gridDim.x) {
+    const PkOpBlock b = k.a.blocks[i];
+    op_products_k(k, b, t, s);
+    __syncthreads();
+    if (b.n_rows >= 0) {      // (uniform over the workgroup)
+      op_row_sums_k(k, b, t, s);
+    } else {
+      op_tree_k(s, t, k.kc);
+      if (t < k.kc) op_store_partial_k(k, b, t, s);
+    }
+    __syncthreads();          // the next block of this workgroup's stride overwrites the planes
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_op_long_k(PkOpArgsK k) {
+  __shared__ double s[PK_OP_KMAX * PK_OP_LDS];
+  const int t = (int)threadIdx.x;
+  for (int32_t i = (int32_t)blockIdx.x; i < k.a.n_longs; i += (int32_t)gridDim.x) {
+    const PkOpLong l = k.a.longs[i];
+    op_long_strided_k(k, l, t, s);
+    __syncthreads();
+    op_tree_k(s, t, k.kc);
+    if (t < k.kc) op_store_long_k(k, l, t, s);
+    __syncthreads();
+  }
+}
 #else
 // ---------------------------------------------------------------- host stand-in: the identical walk over the same tables
 static void op_tree_host(double* s) {
@@ -164,6 +295,39 @@ static void op_long_host(const PkOpArgs& a, unsigned grid) {
       a.y[l.row] = a.add ? s[0] + a.add[l.row] : s[0];
     }
 }
+
+static void op_tree_k_host(double* s, int kc) {
+  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1)
+    for (int t = 0; t < PK_BLOCK; ++t) op_tree_step_k(s, w, t, kc);
+}
+
+static void op_rows_k_host(const PkOpArgsK& k, unsigned grid) {
+  std::vector<double> planes((size_t)PK_OP_KMAX * PK_OP_LDS);
+  double* s = planes.data();
+  for (unsigned wg = 0; wg < grid; ++wg)
+    for (int32_t i = (int32_t)wg; i < k.a.n_blocks; i += (int32_t)grid) {
+      const PkOpBlock b = k.a.blocks[i];
+      for (int t = 0; t < PK_BLOCK; ++t) op_products_k(k, b, t, s);
+      if (b.n_rows >= 0) {
+        for (int t = 0; t < PK_BLOCK; ++t) op_row_sums_k(k, b, t, s);
+      } else {
+        op_tree_k_host(s, k.kc);
+        for (int t = 0; t < k.kc; ++t) op_store_partial_k(k, b, t, s);
+      }
+    }
+}
+
+static void op_long_k_host(const PkOpArgsK& k, unsigned grid) {
+  std::vector<double> planes((size_t)PK_OP_KMAX * PK_OP_LDS);
+  double* s = planes.data();
+  for (unsigned wg = 0; wg < grid; ++wg)
+    for (int32_t i = (int32_t)wg; i < k.a.n_longs; i += (int32_t)grid) {
+      const PkOpLong l = k.a.longs[i];
+      for (int t = 0; t < PK_BLOCK; ++t) op_long_strided_k(k, l, t, s);
+      op_tree_k_host(s, k.kc);
+      for (int t = 0; t < k.kc; ++t) op_store_long_k(k, l, t, s);
+    }
+}
 #endif
 
 // The grid rule of both kernels, stated once: one workgroup per work item up to PK_OP_GRID_CAP (8 workgroups of 256 threads
@@ -173,12 +337,14 @@ static unsigned op_grid(int32_t items) { return (unsigned)std::min<int32_t>(item
 
 static void free_operator(PkOperator& o) {
   release(o.d_indptr); release(o.d_indices); release(o.d_src); release(o.d_blocks); release(o.d_longs); release(o.d_partial);
+  release(o.d_partial_k);
   o = PkOperator{};
 }
 
 void free_operators(pk_ctx* c) {
   for (auto& o : c->ops.op) free_operator(o);
   release(c->ops.d_v); release(c->ops.d_y);
+  c->ops.scratch_k = 0;
   c->ops.lin_J = c->ops.lin_H = nullptr;
 }
 
@@ -231,8 +397,9 @@ int pk_set_csr_operator(pk_ctx* c, int op, const int32_t* indptr, const int32_t*
     const size_t len = (size_t)std::max(c->n, c->m);
     PK_HIP(c, hipMalloc((void**)&c->ops.d_v, sizeof(double) * len));
     PK_HIP(c, hipMalloc((void**)&c->ops.d_y, sizeof(double) * len));
+    c->ops.scratch_k = 1;
   }
-  o.n_rows = n_rows; o.n_cols = n_cols; o.nnz = nnz;
+  o.n_rows = n_rows; o.n_cols = n_cols; o.nnz = nnz; o.n_slots = n_slots;
   o.n_blocks = (int32_t)blocks.size(); o.n_longs = (int32_t)longs.size();
   return 0;
 }
@@ -265,6 +432,50 @@ int pk_apply_operator_dev(pk_ctx* c, int op, const double* d_vals, const double*
   return 0;
 }
 
+int pk_apply_operator_block_dev(pk_ctx* c, int op, const double* d_vals, int32_t k, const double* d_V, int64_t ldv,
+                                const double* d_Add, double* d_Y, int64_t ldy, void* stream) {
+  int rc = ready(c);
+  if (rc) return rc;
+  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator_block: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  PkOperator& o = c->ops.op[op];
+  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator_block: call pk_set_csr_operator(%d) first", op);
+  if (!d_vals || !d_V || !d_Y) return fail(c, 110, "pk_apply_operator_block: null device pointer");
+  if (k < 1) return fail(c, 120, "pk_apply_operator_block: k = %d, a block has at least one column", k);
+  if (ldv < k || ldy < k)
+    return fail(c, 121, "pk_apply_operator_block: leading dimensions %lld / %lld are smaller than k = %d", (long long)ldv, (long long)ldy, k);
+  if (o.n_longs && !o.d_partial_k) {      // the first block product of an operator with long rows
+    PK_HIP(c, hipSetDevice(c->device));
+    if (hipMalloc((void**)&o.d_partial_k, sizeof(double) * (size_t)o.n_slots * PK_OP_KMAX) != hipSuccess) {
+      o.d_partial_k = nullptr;
+      return fail(c, 122, "pk_apply_operator_block: no device memory for %d x %d partial sums", o.n_slots, (int)PK_OP_KMAX);
+    }
+  }
+  PkOpArgsK a{};
+  a.a.blocks = o.d_blocks; a.a.longs = o.d_longs; a.a.indptr = o.d_indptr; a.a.indices = o.d_indices; a.a.src = o.d_src;
+  a.a.vals = d_vals; a.a.partial = o.d_partial_k;
+  a.a.n_blocks = o.n_blocks; a.a.n_longs = o.n_longs;
+  a.ldv = ldv; a.ldy = ldy;
+  hipStream_t st = pick(c, stream);
+  const unsigned grid = op_grid(o.n_blocks), grid_long = op_grid(o.n_longs);
+  // chunks of PK_OP_KMAX columns, the last one narrower; the launches are ordered by the stream, so they share the partial sums
+  for (int32_t c0 = 0; c0 < k; c0 += PK_OP_KMAX) {
+    a.kc = std::min<int32_t>(PK_OP_KMAX, k - c0);
+    a.a.v = d_V + c0; a.a.add = d_Add ? d_Add + c0 : nullptr; a.a.y = d_Y + c0;
+#ifdef __HIPCC__
+    hipLaunchKernelGGL(pk_op_rows_k, dim3(grid), dim3(PK_BLOCK), 0, st, a);
+    PK_HIP(c, hipGetLastError());
+    if (grid_long) {
+      hipLaunchKernelGGL(pk_op_long_k, dim3(grid_long), dim3(PK_BLOCK), 0, st, a);
+      PK_HIP(c, hipGetLastError());
+    }
+#else
+    fake_hip_enqueue(st, [a, grid]() { op_rows_k_host(a, grid); });
+    if (grid_long) fake_hip_enqueue(st, [a, grid_long]() { op_long_k_host(a, grid_long); });
+#endif
+  }
+  return 0;
+}
+
 int pk_linearize(pk_ctx* c, const double* x, const double* lambda, double sigma) {
   if (const int rc = host_ready(c, x != nullptr)) return rc;
   const PkCsrMap& mj = c->csr[c->csr[3].n_unique > 0 ? 3 : 0];      // (the value arrays pk_eval_jac_csr / pk_eval_hess_csr choose)
@@ -294,6 +505,38 @@ int pk_apply_operator(pk_ctx* c, int op, const double* v, double* y) {
   PK_HIP(c, hipMemcpyAsync(c->ops.d_v, v, sizeof(double) * (size_t)o.n_cols, hipMemcpyHostToDevice, c->stream));
   if (const int rc = pk_apply_operator_dev(c, op, vals, c->ops.d_v, nullptr, c->ops.d_y, nullptr)) return rc;
   PK_HIP(c, hipMemcpyAsync(y, c->ops.d_y, sizeof(double) * (size_t)o.n_rows, hipMemcpyDeviceToHost, c->stream));
+  PK_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int pk_apply_operator_block(pk_ctx* c, int op, int32_t k, const double* V, double* Y) {
+  if (const int rc = host_ready(c, V && Y)) return rc;
+  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator_block: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  const PkOperator& o = c->ops.op[op];
+  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator_block: call pk_set_csr_operator(%d) first", op);
+  const double* vals = op == 2 ? c->ops.lin_H : c->ops.lin_J;
+  if (!vals && op == 2 && c->ops.lin_J) return fail(c, 118, "pk_apply_operator_block: the linearization has no Hessian (pk_linearize without lambda)");
+  if (!vals) return fail(c, 118, "pk_apply_operator_block: no linearization (pk_linearize)");
+  if (k < 1) return fail(c, 120, "pk_apply_operator_block: k = %d, a block has at least one column", k);
+  PK_HIP(c, hipSetDevice(c->device));
+  if (k > c->ops.scratch_k) {      // the scratch grows to the widest block seen and never shrinks short of free_operators
+    const size_t len = (size_t)std::max(c->n, c->m) * (size_t)k;
+    double *v = nullptr, *y = nullptr;
+    if (hipMalloc((void**)&v, sizeof(double) * len) != hipSuccess || hipMalloc((void**)&y, sizeof(double) * len) != hipSuccess) {
+      release(v);
+      return fail(c, 122, "pk_apply_operator_block: no device memory for two scratch blocks of %zu doubles", len);
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);      // (a product enqueued earlier may still read the old ones)
+    if (e != hipSuccess) {
+      release(v); release(y);
+      return fail(c, 100 + (int)e, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    release(c->ops.d_v); release(c->ops.d_y);
+    c->ops.d_v = v; c->ops.d_y = y; c->ops.scratch_k = k;
+  }
+  PK_HIP(c, hipMemcpyAsync(c->ops.d_v, V, sizeof(double) * (size_t)o.n_cols * (size_t)k, hipMemcpyHostToDevice, c->stream));
+  if (const int rc = pk_apply_operator_block_dev(c, op, vals, k, c->ops.d_v, k, nullptr, c->ops.d_y, k, nullptr)) return rc;
+  PK_HIP(c, hipMemcpyAsync(Y, c->ops.d_y, sizeof(double) * (size_t)o.n_rows * (size_t)k, hipMemcpyDeviceToHost, c->stream));
   PK_HIP(c, hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -6,7 +6,8 @@
 //   pk_shard.cpp    sharding: shard flags, peer / IPC / registered memory, the exchange of the partial sums, run copies
 //   pk_batch.cpp    a batch of iterates in one launch of the fused cycle (pk_cycleb): batched object, per-entry workspaces
 //   pk_extras.cpp   CSR hand-off, mesh error estimation, profiling and developer tracing
-//   pk_ops.cpp      J, J^T and the symmetric H applied to vectors on the device (pk_op_rows, pk_op_long: the library's own kernels)
+//   pk_ops.cpp      J, J^T and the symmetric H applied to vectors and blocks of vectors on the device (pk_op_rows, pk_op_long,
+//                   pk_op_rows_k, pk_op_long_k: the library's own kernels)
 //   pk_error.cpp    fail(): where an error message is kept
 //
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
@@ -122,6 +123,7 @@ struct PkCsrMap {
 struct PkOpBlock {
   int32_t e0, count, row0, n_rows;
 };
+enum { PK_OP_KMAX = 8 };      // columns of a block product one workgroup handles: a wider block goes in chunks of launches
 struct PkOpLong {      // a row with more than PK_BLOCK entries: its partial sums are the slots [first, first + pieces)
   int32_t row, first, pieces;
 };
@@ -130,12 +132,15 @@ struct PkOperator {
   PkOpBlock* d_blocks = nullptr;
   PkOpLong* d_longs = nullptr;
   double* d_partial = nullptr;
+  double* d_partial_k = nullptr;      // the block product's partial sums, n_slots x PK_OP_KMAX: allocated on its first use
   int32_t n_rows = 0, n_cols = 0, n_blocks = 0, n_longs = 0;             // n_blocks = 0: not set
+  int32_t n_slots = 0;
   int64_t nnz = 0;
 };
 struct PkOps {
   PkOperator op[3];                          // 0 J, 1 J^T, 2 H symmetric
-  double *d_v = nullptr, *d_y = nullptr;     // scratch vectors of pk_apply_operator, max(n, m) doubles each
+  double *d_v = nullptr, *d_y = nullptr;     // scratch of pk_apply_operator[_block], max(n, m) * scratch_k doubles each
+  int64_t scratch_k = 0;                     // columns they hold (1 from pk_set_csr_operator; pk_apply_operator_block grows them)
   const double *lin_J = nullptr, *lin_H = nullptr;   // the linearization of pk_linearize: CSR value arrays of the maps (NULL: none)
 };
 

@@ -886,6 +886,16 @@ class Evaluator:
         k = self._operator(op)
         self.ctx.check(self.ctx.lib.pk_apply_operator_dev(self.ctx.handle, k, d_vals, d_v, d_add, d_y, stream))
 
+    def apply_operator_block_dev(self, op, d_vals, k, d_V, d_Y, ldv=None, ldy=None, d_add=None, stream=None):
+        """``Y = A(vals) V (+ Add)`` on device pointers for a block of ``k`` vectors, row-major: ``V[i * ldv + j]``,
+        ``Y[r * ldy + j]`` (and ``Add`` like ``Y``), ``ldv`` / ``ldy`` defaulting to ``k`` -- the C order of an ``(n, k)``
+        tensor.  Only the first ``k`` entries of a row of ``Y`` are written.  Column ``j`` has the bits ``apply_operator_dev``
+        gives for column ``j`` alone.  ``d_add`` may alias ``d_Y``.  Enqueued on ``stream``, not waited for."""
+        num = self._operator(op)
+        k = int(k)
+        self.ctx.check(self.ctx.lib.pk_apply_operator_block_dev(self.ctx.handle, num, d_vals, k, d_V, k if ldv is None else int(ldv),
+                                                                d_add, d_Y, k if ldy is None else int(ldy), stream))
+
     def linearize(self, x, lagrange=None, obj_factor=1.0):
         """Evaluate J at ``x`` -- and the Hessian of the Lagrangian with ``(lagrange, obj_factor)`` unless ``lagrange`` is
         None -- into the context's CSR value arrays and leave them on the device: the ``Linearization`` returned multiplies
@@ -1181,6 +1191,32 @@ class Linearization:
         ev.ctx.check(ev.ctx.lib.pk_apply_operator(ev.ctx.handle, ev.OPERATORS[op], runtime.as_dp(v), runtime.as_dp(y)))
         return y
 
+    def _apply_block(self, op, V, n_in, n_out):
+        ev = self._ev
+        if ev.ctx is None or self._gen != ev._lin_gen:
+            raise RuntimeError("stale linearization: the evaluator has been given another evaluation since (one linearization per context)")
+        V = np.asarray(V, dtype=np.float64)
+        if V.ndim != 2 or V.shape[0] != n_in or V.shape[1] < 1:
+            raise ValueError(f"the block must have shape ({n_in}, k) with k >= 1")
+        V = np.ascontiguousarray(V)
+        Y = np.empty((n_out, V.shape[1]))
+        ev.ctx.check(ev.ctx.lib.pk_apply_operator_block(ev.ctx.handle, ev.OPERATORS[op], V.shape[1], runtime.as_dp(V), runtime.as_dp(Y)))
+        return Y
+
+    def jmat(self, V):
+        """``J V`` for a block ``V`` of shape (n, k), any memory order: (m, k), column j with the bits of ``jv(V[:, j])``"""
+        return self._apply_block("J", V, self.n, self.m)
+
+    def jtmat(self, Y):
+        """``J^T Y`` for a block ``Y`` of shape (m, k): (n, k)"""
+        return self._apply_block("JT", Y, self.m, self.n)
+
+    def hmat(self, V):
+        """``H V`` with the full symmetric Hessian of the Lagrangian for a block ``V`` of shape (n, k): (n, k)"""
+        if not self.has_hessian:
+            raise RuntimeError("this linearization has no Hessian: linearize(x, lagrange, obj_factor)")
+        return self._apply_block("H", V, self.n, self.n)
+
     def jv(self, v):
         """``J v``"""
         return self._apply("J", v, self.n, self.m)
@@ -1199,10 +1235,11 @@ class Linearization:
         from scipy.sparse.linalg import LinearOperator
 
         flat = lambda f: lambda v: f(np.asarray(v).reshape(-1))  # noqa: E731  (SciPy also passes columns)
-        return LinearOperator((self.m, self.n), matvec=flat(self.jv), rmatvec=flat(self.jtv), dtype=np.float64)
+        return LinearOperator((self.m, self.n), matvec=flat(self.jv), rmatvec=flat(self.jtv), matmat=self.jmat, rmatmat=self.jtmat,
+                              dtype=np.float64)
 
     def hessian_operator(self):
         from scipy.sparse.linalg import LinearOperator
 
         hv = lambda v: self.hv(np.asarray(v).reshape(-1))  # noqa: E731
-        return LinearOperator((self.n, self.n), matvec=hv, rmatvec=hv, dtype=np.float64)
+        return LinearOperator((self.n, self.n), matvec=hv, rmatvec=hv, matmat=self.hmat, rmatmat=self.hmat, dtype=np.float64)

@@ -101,6 +101,8 @@ PROTOTYPES = {
     "pk_apply_operator_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
     "pk_linearize": (C.c_int, [vp, dp, dp, C.c_double]),
     "pk_apply_operator": (C.c_int, [vp, C.c_int, dp, dp]),
+    "pk_apply_operator_block_dev": (C.c_int, [vp, C.c_int, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, vp]),
+    "pk_apply_operator_block": (C.c_int, [vp, C.c_int, C.c_int32, dp, dp]),
     "pk_eval_f_dev": (C.c_int, [vp, vp, vp, vp]),
     "pk_eval_grad_dev": (C.c_int, [vp, vp, vp, vp]),
     "pk_eval_g_dev": (C.c_int, [vp, vp, vp, vp]),
