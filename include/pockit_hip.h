@@ -1,6 +1,6 @@
 /* pockit_hip.h -- C ABI of the MI355X NLP-callback evaluator (libpockit_hip.so).
  *
- * STABLE SURFACE.  The 44 entry points declared here are the contract of the library: what a second host binding for
+ * STABLE SURFACE.  The 49 entry points declared here are the contract of the library: what a second host binding for
  * pockit's evaluator path needs -- life cycle, evaluation on host buffers and on device pointers, the compact layouts, the CSR
  * hand-off and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
  * shim, the sharding transport, the helper threads, tuning switches and diagnostics) is declared in
@@ -276,6 +276,46 @@ int pk_eval_cycle_batch_dev(pk_ctx* ctx, int B, const double* d_x, int64_t ldx, 
                             const double* sigma /* host, B values */, double* d_f, double* d_grad, double* d_g,
                             double* d_jac, double* d_hess, void* stream);
 int pk_sync(pk_ctx* ctx, void* stream);
+
+/* MERIT TERMS of a batch of trial points, reduced on the device (kernels pk_trial, pk_merit, pk_merit_fin of the library): what
+ * a line search or a multi-start ranking wants back from a batch is a handful of scalars per point, not J.  Per entry b a row
+ * of 8 doubles out[b * 8 + q]:
+ *   0 f[b]                                              4 bound1     sum_i viol(X[b,i], v_lb[i], v_ub[i])
+ *   1 theta1     sum_i viol(g[b,i], c_lb[i], c_ub[i])   5 bound_inf  max_i of the same
+ *   2 theta_inf  max_i of the same                      6 slope      sum_i grad[b,i] * d[i], 0.0 when d is NULL
+ *   3 theta2_sq  sum_i viol^2                           7 bad        non-finite values among f[b], g[b,:], grad[b,:]
+ * viol(v, lo, hi) = max(lo - v, v - hi, 0); bounds may be infinite.  A non-finite g or grad entry is counted in column 7 and
+ * adds nothing elsewhere: the other columns stay finite and the caller rejects the point on out[b * 8 + 7] > 0.  Every square
+ * and product is rounded before it is added (no fused multiply-add); the association of the sums is fixed (pk_merit.cpp,
+ * DESIGN.md section 16) and depends neither on the grid nor on the run: no atomics, the same bits every time.
+ *
+ * pk_set_bounds: host arrays of m, m, n, n doubles, validated and uploaded (error 126: a null pointer, a NaN, lb > ub);
+ * pk_set_problem drops them.
+ * pk_trial_points_dev: X[b * ldx + i] = x[i] + alpha[b] * d[i] for b < B <= PK_MAX_BATCH, with exactly the bits of the
+ * rounded product added to x[i]; ``alpha``: B values in HOST memory, read before the call returns (they travel in the kernel
+ * arguments).
+ * pk_merit_batch_dev: the rows of B <= PK_MAX_BATCH entries from device arrays as pk_eval_cycle_batch_dev leaves them (rows of
+ * g / grad / X ldg >= m / ldgrad >= n / ldx >= n doubles apart, f dense), measured against the uploaded bounds; d_d (n values)
+ * may be NULL.  Two launches on ``stream``, not waited for.  The partial results lie in an array of the context that grows when
+ * needed: one reduction may be in flight per context at a time.
+ * pk_merit_scan / pk_merit_batch: the host forms.  They upload (x, d and form the trial points; or the rows of X, ldx >= n
+ * doubles apart), run the x-only batch (pk_eval_cycle_batch_dev without lambda) into scratch the context owns -- one slice
+ * per entry -- and the two reduction launches, download 8 * B doubles into ``out`` and synchronize once.  B has no upper
+ * limit: they walk it in chunks of min(PK_MAX_BATCH, max(1, 256 MiB / (8 (nnz_J + n + m + 1)))) entries, which bounds the
+ * scratch; it grows when needed, never shrinks, and is freed by pk_set_problem.  A context whose batch is served by the loop
+ * of single cycles gives the same values.
+ * Errors: 123 no bounds set; 124 B < 1, or above PK_MAX_BATCH in a _dev form; 125 a leading dimension below its length;
+ * 126 bounds rejected; 127 no device memory (nothing is enqueued, what was there stays); 128 a null device pointer; 60 a null
+ * host buffer; 88 (host forms) a compact cycle layout or a sharded context with the in-launch exchange, as for the batch. */
+int pk_set_bounds(pk_ctx* ctx, const double* c_lb /* m */, const double* c_ub /* m */, const double* v_lb /* n */,
+                  const double* v_ub /* n */);
+int pk_trial_points_dev(pk_ctx* ctx, int B, const double* d_x, const double* d_d, const double* alpha /* host, B values */,
+                        double* d_X, int64_t ldx, void* stream);
+int pk_merit_batch_dev(pk_ctx* ctx, int B, const double* d_f, const double* d_g, int64_t ldg, const double* d_grad,
+                       int64_t ldgrad, const double* d_X, int64_t ldx, const double* d_d /* or NULL */, double* d_out /* B x 8 */,
+                       void* stream);
+int pk_merit_scan(pk_ctx* ctx, int64_t B, const double* x, const double* d, const double* alpha /* B */, double* out /* B x 8 */);
+int pk_merit_batch(pk_ctx* ctx, int64_t B, const double* X, int64_t ldx, const double* d /* or NULL */, double* out /* B x 8 */);
 
 #ifdef __cplusplus
 }

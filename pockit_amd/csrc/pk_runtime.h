@@ -8,6 +8,8 @@
 //   pk_extras.cpp   CSR hand-off, mesh error estimation, profiling and developer tracing
 //   pk_ops.cpp      J, J^T and the symmetric H applied to vectors and blocks of vectors on the device (pk_op_rows, pk_op_long,
 //                   pk_op_rows_k, pk_op_long_k: the library's own kernels)
+//   pk_merit.cpp    merit terms of a batch of trial points reduced on the device (pk_trial, pk_merit, pk_merit_fin: the library's
+//                   own kernels), the bounds they are measured against, the scratch of the host forms
 //   pk_error.cpp    fail(): where an error message is kept
 //
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
@@ -142,6 +144,15 @@ struct PkOps {
   double *d_v = nullptr, *d_y = nullptr;     // scratch of pk_apply_operator[_block], max(n, m) * scratch_k doubles each
   int64_t scratch_k = 0;                     // columns they hold (1 from pk_set_csr_operator; pk_apply_operator_block grows them)
   const double *lin_J = nullptr, *lin_H = nullptr;   // the linearization of pk_linearize: CSR value arrays of the maps (NULL: none)
+};
+
+// ---- merit terms of a batch of trial points (pk_merit.cpp: pk_set_bounds, pk_merit_batch_dev, pk_merit_scan ...; free_merit)
+struct PkMerit {
+  double* d_bounds = nullptr;       // pk_set_bounds: [c_lb (m) | c_ub (m) | v_lb (n) | v_ub (n)], NULL: not set
+  double* d_partial = nullptr;      // the pieces' partial rows of pk_merit, 8 doubles each: grows when needed, never shrinks
+  size_t partial_cap = 0;           // ... in doubles
+  double* d_scratch = nullptr;      // the host forms' [x | d | X | f | grad | g | J | out] for one chunk of entries: likewise
+  size_t scratch_cap = 0;
 };
 
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
@@ -293,6 +304,7 @@ struct pk_ctx : pk_error_state {
                      // + [2]: compact Hessian values -> the same CSR entries (a pure permutation: one value per entry)
                      // + [3]: compact Jacobian values -> the CSR entries of J (the few repeated positions summed)
   PkOps ops;
+  PkMerit merit;
   PkMeshError mesh_error;
   PkShim shim;
 };
@@ -376,6 +388,9 @@ void drop_linearization(pk_ctx* c);  // the CSR value arrays of the maps are abo
 // row with more than PK_BLOCK entries, and the list of those long rows.  Pure; nonzero: a count does not fit 32 bits.
 int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBlock>& blocks, std::vector<PkOpLong>& longs,
                      int32_t& n_slots);
+
+// ---- pk_merit.cpp
+void free_merit(pk_ctx* c);          // bounds, partial rows and scratch (with the problem)
 
 // ---- the host-buffer form of an entry point: upload x (and lambda), the device-pointer entry point, download, synchronize
 inline int host_ready(pk_ctx* c, bool buffers) {

@@ -172,7 +172,7 @@ int pk_copy_runs_dev(pk_ctx* ctx, const int64_t* d_table, int n_chunks, const do
  * poll such words instead of waiting for the other processes to notice that their GPU has finished) */
 int pk_store_word_dev(pk_ctx* ctx, void* d_dst, int64_t value, void* stream);
 
-/* ================================================================================================ Tuning and diagnostics (9) */
+/* ================================================================================================ Tuning and diagnostics (10) */
 /* `count` back-to-back cycles on the same buffers, enqueued by the library (a solver written against the C ABI launches from
  * compiled code; bench.py's timed batches go through this so that no interpreter loop paces the stream).  xchg = 1: every
  * cycle is followed by pk_exchange_sums_dev(d_x, d_xgrad, d_f) -- the two-launch form of a sharded cycle.  No reference
@@ -202,6 +202,12 @@ const char* pk_kernel_name(int kernel_id);
 /* launches of pk_cycleb by this context so far (counted with or without profiling): a batch served by the loop of single
  * cycles adds none, a batch served by the kernel adds exactly one */
 int pk_batch_launches(pk_ctx* ctx, int64_t* launches);
+/* pk_merit_batch_dev's reduction with EXPLICIT lengths and device bound pointers (the public form calls it with the context's
+ * n, m and uploaded bounds): g has n_g values per entry, X and grad n_x; so that tests can drive lengths a small model does
+ * not have.  Lengths may be 0.  Errors 124, 125, 127, 128 as there. */
+int pk_merit_reduce_dev(pk_ctx* ctx, int B, int64_t n_g, const double* d_g, int64_t ldg, const double* d_clb, const double* d_cub,
+                        int64_t n_x, const double* d_X, int64_t ldx, const double* d_vlb, const double* d_vub, const double* d_grad,
+                        int64_t ldgrad, const double* d_d /* or NULL */, const double* d_f, double* d_out, void* stream);
 
 #ifdef __cplusplus
 }

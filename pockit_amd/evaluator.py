@@ -439,6 +439,8 @@ class Evaluator:
         self._output_share = float(output_share)
         self._batch_state = None     # None: not decided; "kernel": pk_cycleb loaded and verified; "loop": single cycles (see _ensure_batch)
         self._batch_bufs = (0, None)
+        self._bounds = None          # what set_bounds was given (None: the plan's); _bounds_up: they are on the device
+        self._bounds_up = False
         # (compiled before the context is created: a box without a GPU -- the build container -- can still fill the
         # code-object cache by constructing evaluators, tools/warm_cache.sh)
         self.src, code = compile_plan(plan, sharded=sharded, output_share=output_share, extra_flags=self.hipcc_flags, fixed=_fixed)
@@ -466,6 +468,7 @@ class Evaluator:
         self.tables = tb
         self._views = {}
         self._csr, self._ops = {}, {}      # (pk_set_problem frees the maps and the operators of the context)
+        self._bounds, self._bounds_up = None, False      # (... and the uploaded bounds of the merit terms)
         self._lin_gen += 1
         pd = runtime.ProblemDesc()
         pd.n, pd.m, pd.n_sys, pd.n_s, pd.l_s = plan.n, plan.m, plan.n_sys, plan.n_s, plan.l_s
@@ -1118,6 +1121,92 @@ class Evaluator:
         finally:
             self._free_batch_buffers()
         return tuple(out)
+
+    # ------------------------------------------------------------------ merit terms of a batch of trial points (csrc/pk_merit.cpp)
+    def set_bounds(self, c_lb=None, c_ub=None, v_lb=None, v_ub=None):
+        """The bounds the merit terms are measured against: ``(m,), (m,), (n,), (n,)``, each defaulting to the plan's.  They are
+        validated (no NaN, ``lb <= ub``) and uploaded on first use; ``set_tables`` forgets them."""
+        p = self.plan
+        given = (c_lb, c_ub, v_lb, v_ub)
+        out = []
+        for a, default, count in zip(given, (p.c_lb, p.c_ub, p.v_lb, p.v_ub), (p.m, p.m, p.n, p.n)):
+            a = np.ascontiguousarray(default if a is None else a, dtype=np.float64)
+            if a.shape != (count,):
+                raise ValueError(f"bounds must have shapes ({p.m},), ({p.m},), ({p.n},), ({p.n},)")
+            out.append(a.copy())
+        self._bounds, self._bounds_up = tuple(out), False
+
+    def _ensure_merit(self):
+        """What every merit entry point needs first: an unsharded evaluator, the batched code object decided
+        (``_ensure_batch``), the bounds on the device."""
+        if self.src.sharded:
+            raise NotImplementedError("the merit terms of a batch are not offered for a sharded evaluator")
+        self._ensure_batch()
+        if not self._bounds_up:
+            if self._bounds is None:
+                self.set_bounds()
+            self.ctx.check(self.ctx.lib.pk_set_bounds(self.ctx.handle, *(runtime.as_dp(a) for a in self._bounds)))
+            self._bounds_up = True
+
+    def trial_points_dev(self, B, d_x, d_d, alphas, d_X, ldx=None, stream=None):
+        """Enqueue ``X[b] = x + alphas[b] * d`` for ``B`` (at most ``runtime.MAX_BATCH``) host values ``alphas`` on device
+        pointers (ints): the product rounded, then the sum -- the bits of NumPy's ``x + a * d``.  Rows of ``X`` are ``ldx``
+        (default n) doubles apart.  Not waited for."""
+        self._ensure_merit()
+        a = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        if len(a) != int(B):
+            raise ValueError(f"alphas must have {int(B)} values")
+        self._invalidate_x()
+        self.ctx.check(self.ctx.lib.pk_trial_points_dev(self.ctx.handle, int(B), d_x, d_d, runtime.as_dp(a) if len(a) else None, d_X,
+                                                        self.plan.n if ldx is None else int(ldx), stream))
+
+    def merit_batch_dev(self, B, d_f, d_g, d_grad, d_X, d_out, d_d=None, ldg=None, ldgrad=None, ldx=None, stream=None):
+        """Enqueue the reduction of ``B`` entries as ``cycle_batch_dev`` leaves them (device pointers, dense unless a leading
+        dimension says otherwise) to ``(B, 8)`` merit terms at ``d_out`` (columns: ``merit.COLUMNS``); ``d_d``: the direction
+        of the slope column, or None.  Two launches, not waited for."""
+        self._ensure_merit()
+        p = self.plan
+        self._invalidate_x()
+        self.ctx.check(self.ctx.lib.pk_merit_batch_dev(self.ctx.handle, int(B), d_f, d_g, p.m if ldg is None else int(ldg), d_grad,
+                                                       p.n if ldgrad is None else int(ldgrad), d_X, p.n if ldx is None else int(ldx),
+                                                       d_d, d_out, stream))
+
+    def _direction(self, d):
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        if d.shape != (self.plan.n,):
+            raise ValueError(f"d must have shape ({self.plan.n},)")
+        return d
+
+    def merit_batch(self, X, d=None):
+        """The ``(B, 8)`` merit terms (columns: ``merit.COLUMNS``) of the iterates ``X[b]``: the x-only batch and the
+        reduction stay on the device, ``8 B`` doubles come back.  ``d``: the direction of the slope column (0.0 without)."""
+        p = self.plan
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != p.n:
+            raise ValueError(f"X must have shape (B, {p.n})")
+        d = None if d is None else self._direction(d)
+        out = np.empty((X.shape[0], 8))
+        if X.shape[0] == 0:
+            return out
+        self._ensure_merit()
+        self._invalidate_x()
+        self.ctx.check(self.ctx.lib.pk_merit_batch(self.ctx.handle, X.shape[0], runtime.as_dp(X), p.n, None if d is None else runtime.as_dp(d),
+                                                   runtime.as_dp(out)))
+        return out
+
+    def merit_scan(self, x, d, alphas):
+        """The ``(B, 8)`` merit terms of the trial points ``x + alphas[b] * d``, formed on the device: one upload of ``x`` and
+        ``d``, one batch launch and two reduction launches per ``runtime.MAX_BATCH`` points, ``8 B`` doubles back."""
+        x, d = self._x(x), self._direction(d)
+        a = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        out = np.empty((len(a), 8))
+        if len(a) == 0:
+            return out
+        self._ensure_merit()
+        self._invalidate_x()
+        dp = runtime.as_dp
+        self.ctx.check(self.ctx.lib.pk_merit_scan(self.ctx.handle, len(a), dp(x), dp(d), dp(a), dp(out)))
+        return out
 
     def batch_launches(self):
         """Launches of ``pk_cycleb`` by this evaluator so far: a batch served by the loop of single cycles adds none."""

@@ -674,6 +674,25 @@ class SystemBase:
         (``Evaluator.cycle_batch``); ``Lam = None``: the x-only outputs, H is None.  Reference layouts."""
         return self.evaluator.cycle_batch(X, Lam, sigma)
 
+    def merit_batch(self, X, d=None):
+        """The merit terms of the ``B`` iterates ``X[b]``, reduced on the GPU -- ``8 B`` doubles come back instead of grad f, g
+        and J of every entry.  Returns a read-only ``merit.MeritTable`` (the ``(B, 8)`` array is ``.table``) with the columns
+        ``f``; ``theta1``, ``theta_inf``, ``theta2_sq``: sum, maximum and sum of squares over i of
+        ``viol(g_i, c_lb_i, c_ub_i)`` with ``viol(v, lo, hi) = max(lo - v, v - hi, 0)``; ``bound1``, ``bound_inf``: sum and
+        maximum of ``viol(x_i, v_lb_i, v_ub_i)``; ``slope``: ``grad f . d`` (0.0 without ``d``); ``bad``: the number of
+        non-finite values among f, g and grad f of the entry, which are left out of every other column -- reject a point on
+        ``bad > 0``.  Squares and products are rounded before they are added, in a fixed order."""
+        from .merit import MeritTable
+
+        return MeritTable(self.evaluator.merit_batch(X, d))
+
+    def merit_scan(self, x, d, alphas):
+        """``merit_batch`` of the trial points ``x + alphas[b] * d``, which are formed on the GPU (the bits of NumPy's
+        ``x + a * d``): what a backtracking or filter line search asks per scan."""
+        from .merit import MeritTable
+
+        return MeritTable(self.evaluator.merit_scan(x, d, alphas))
+
     # split Hessians used by the SciPy adapter (reference: systembase.py:726-809)
     def hessianstructure_o(self):
         if self._hessian_layout == "compact":

@@ -115,6 +115,11 @@ PROTOTYPES = {
     "pk_set_batch": (C.c_int, [vp, C.c_int]),
     "pk_eval_cycle_batch_dev": (C.c_int, [vp, C.c_int, vp, C.c_int64, vp, C.c_int64, dp, vp, vp, vp, vp, vp, vp]),
     "pk_sync": (C.c_int, [vp, vp]),
+    "pk_set_bounds": (C.c_int, [vp, dp, dp, dp, dp]),
+    "pk_trial_points_dev": (C.c_int, [vp, C.c_int, vp, vp, dp, vp, C.c_int64, vp]),
+    "pk_merit_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]),
+    "pk_merit_scan": (C.c_int, [vp, C.c_int64, dp, dp, dp, dp]),
+    "pk_merit_batch": (C.c_int, [vp, C.c_int64, dp, C.c_int64, dp, dp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -175,6 +180,8 @@ PROTOTYPES = {
     "pk_profile_read": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64), dp]),
     "pk_batch_launches": (C.c_int, [vp, C.POINTER(C.c_int64)]),
     "pk_kernel_name": (C.c_char_p, [C.c_int]),
+    "pk_merit_reduce_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64,
+                                      vp, vp, vp, vp]),
 }
 EXPORTS = list(PROTOTYPES)
 
