@@ -19,7 +19,7 @@
 // belongs to piece p = i / 2048; thread t of the piece adds the terms of p * 2048 + t + 256 j for j = 0 ... 7 in ascending j
 // to 0.0 (coalesced reads; an index beyond a vector's length adds nothing), every square and every product rounded before it
 // is added.  The 256 thread values meet in LDS and are reduced by the tree of widths 128, 64 ... 1 (slot t += slot t + w)
-// that pk_ops.cpp uses.  pk_merit_fin: thread t adds the rows of the pieces t, t + 256, ... in ascending order to 0.0, the
+// of pk_libkernel.h.  pk_merit_fin: thread t adds the rows of the pieces t, t + 256, ... in ascending order to 0.0, the
 // same tree follows, thread q < 8 stores column q.  Columns 2 and 5 walk the same way with max in place of +; column 7 counts.
 // n_pieces = max(1, ceil(max(len g, len X) / 2048)): g, X and grad share the pieces, the shorter vector ends earlier.
 #include "pk_runtime.h"
@@ -32,14 +32,9 @@
 #pragma GCC optimize("fp-contract=off")
 #endif
 
-#ifdef __HIPCC__
-#define PK_MERIT_FN __host__ __device__ __forceinline__
-#else
-#define PK_MERIT_FN inline
-#endif
+#include "pk_libkernel.h"      // (behind the pragma: what its templates are instantiated with is this unit's arithmetic)
 
 enum { PK_MERIT_PER_THREAD = 8, PK_MERIT_PIECE = PK_BLOCK * PK_MERIT_PER_THREAD, PK_MERIT_COLS = 8, PK_MERIT_PLANES = 7 };
-static_assert((PK_BLOCK & (PK_BLOCK - 1)) == 0, "the tree halves the workgroup");
 
 struct PkMeritArgs {
   const double *g, *clb, *cub;      // n_g values per entry, rows ldg apart; the bounds are shared by the entries
@@ -59,7 +54,7 @@ struct PkTrialArgs {
   double alpha[PK_MAX_BATCH];
 };
 
-PK_MERIT_FN double merit_viol(double v, double lo, double hi) {
+PK_LIB_FN double merit_viol(double v, double lo, double hi) {
   const double a = lo - v, b = v - hi;
   double r = 0.0;
   if (a > r) r = a;
@@ -67,11 +62,11 @@ PK_MERIT_FN double merit_viol(double v, double lo, double hi) {
   return r;
 }
 
-PK_MERIT_FN bool merit_is_max(int q) { return q == 2 || q == 5; }
-PK_MERIT_FN double merit_combine(int q, double a, double b) { return merit_is_max(q) ? (b > a ? b : a) : a + b; }
+PK_LIB_FN bool merit_is_max(int q) { return q == 2 || q == 5; }
+PK_LIB_FN double merit_combine(int q, double a, double b) { return merit_is_max(q) ? (b > a ? b : a) : a + b; }
 
 // thread t of piece p of entry b: its seven values (columns 1 ... 7) into the planes, plane q - 1 for column q
-PK_MERIT_FN void merit_thread(const PkMeritArgs& a, int32_t b, int64_t p, int t, double* s) {
+PK_LIB_FN void merit_thread(const PkMeritArgs& a, int32_t b, int64_t p, int t, double* s) {
   const double* g = a.g + (int64_t)b * a.ldg;
   const double* X = a.X + (int64_t)b * a.ldx;
   const double* grad = a.grad + (int64_t)b * a.ldgrad;
@@ -108,7 +103,7 @@ PK_MERIT_FN void merit_thread(const PkMeritArgs& a, int32_t b, int64_t p, int t,
 }
 
 // thread t of entry b in pk_merit_fin: per column the rows of the pieces t, t + 256, ... in ascending order
-PK_MERIT_FN void merit_fin_thread(const PkMeritArgs& a, int32_t b, int t, double* s) {
+PK_LIB_FN void merit_fin_thread(const PkMeritArgs& a, int32_t b, int t, double* s) {
   const double* rows = a.partial + (int64_t)b * a.n_pieces * PK_MERIT_COLS;
   for (int q = 1; q < PK_MERIT_COLS; ++q) {
     double acc = 0.0;
@@ -119,7 +114,7 @@ PK_MERIT_FN void merit_fin_thread(const PkMeritArgs& a, int32_t b, int t, double
 
 // one step of the seven trees, which share the barrier of the level: widths 128, 64 ... 1.  The lanes of a wave work on
 // consecutive doubles of one plane at a time: no bank is asked twice by a half-wave.
-PK_MERIT_FN void merit_tree_step(double* s, int w, int t) {
+PK_LIB_FN void merit_tree_step(double* s, int w, int t) {
   if (t >= w) return;
   for (int q = 1; q < PK_MERIT_COLS; ++q) {
     double* p = s + (q - 1) * PK_BLOCK;
@@ -128,18 +123,20 @@ PK_MERIT_FN void merit_tree_step(double* s, int w, int t) {
 }
 
 // thread q < 8 behind the trees
-PK_MERIT_FN void merit_store_partial(const PkMeritArgs& a, int64_t item, int q, const double* s) {
+PK_LIB_FN void merit_store_partial(const PkMeritArgs& a, int64_t item, int q, const double* s) {
   a.partial[item * PK_MERIT_COLS + q] = q == 0 ? 0.0 : s[(q - 1) * PK_BLOCK];
 }
-PK_MERIT_FN void merit_store_out(const PkMeritArgs& a, int32_t b, int q, const double* s) {
+PK_LIB_FN void merit_store_out(const PkMeritArgs& a, int32_t b, int q, const double* s) {
   const double f = a.f[b];
   double v = q == 0 ? f : s[(q - 1) * PK_BLOCK];
   if (q == 7 && !__builtin_isfinite(f)) v = v + 1.0;
   a.out[(int64_t)b * PK_MERIT_COLS + q] = v;
 }
 
+static int64_t trial_items(int64_t n) { return (n + PK_BLOCK - 1) / PK_BLOCK; }
+
 // element i of every trial point: x[i] and d[i] are read once
-PK_MERIT_FN void trial_element(const PkTrialArgs& a, int32_t i) {
+PK_LIB_FN void trial_element(const PkTrialArgs& a, int32_t i) {
   const double xi = a.x[i], di = a.d[i];
   for (int32_t b = 0; b < a.B; ++b) {
     const double step = a.alpha[b] * di;
@@ -149,13 +146,6 @@ PK_MERIT_FN void trial_element(const PkTrialArgs& a, int32_t i) {
 
 #ifdef __HIPCC__
 // ---------------------------------------------------------------- kernels (gfx950)
-__device__ __forceinline__ void merit_tree(double* s, int t) {      // (every thread of the workgroup)
-  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1) {
-    merit_tree_step(s, w, t);
-    __syncthreads();
-  }
-}
-
 __global__ void __launch_bounds__(PK_BLOCK) pk_merit(PkMeritArgs a) {
   __shared__ double s[PK_MERIT_PLANES * PK_BLOCK];
   const int t = (int)threadIdx.x;
@@ -164,7 +154,7 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_merit(PkMeritArgs a) {
     const int32_t b = (int32_t)(item / a.n_pieces);
     merit_thread(a, b, item - (int64_t)b * a.n_pieces, t, s);
     __syncthreads();
-    merit_tree(s, t);
+    lib_tree(merit_tree_step, s, t);
     if (t < PK_MERIT_COLS) merit_store_partial(a, item, t, s);
     __syncthreads();          // the next item of this workgroup's stride overwrites the planes
   }
@@ -176,7 +166,7 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_merit_fin(PkMeritArgs a) {
   for (int32_t b = (int32_t)blockIdx.x; b < a.B; b += (int32_t)gridDim.x) {
     merit_fin_thread(a, b, t, s);
     __syncthreads();
-    merit_tree(s, t);
+    lib_tree(merit_tree_step, s, t);
     if (t < PK_MERIT_COLS) merit_store_out(a, b, t, s);
     __syncthreads();
   }
@@ -188,45 +178,34 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_trial(PkTrialArgs a) {
 }
 #else
 // ---------------------------------------------------------------- host stand-in: the identical walk
-static void merit_tree_host(double* s) {
-  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1)
-    for (int t = 0; t < PK_BLOCK; ++t) merit_tree_step(s, w, t);
-}
-
 static void merit_host(const PkMeritArgs& a, unsigned grid) {
   double s[PK_MERIT_PLANES * PK_BLOCK];
-  const int64_t items = (int64_t)a.B * a.n_pieces;
-  for (unsigned wg = 0; wg < grid; ++wg)
-    for (int64_t item = wg; item < items; item += grid) {
-      const int32_t b = (int32_t)(item / a.n_pieces);
-      for (int t = 0; t < PK_BLOCK; ++t) merit_thread(a, b, item - (int64_t)b * a.n_pieces, t, s);
-      merit_tree_host(s);
-      for (int q = 0; q < PK_MERIT_COLS; ++q) merit_store_partial(a, item, q, s);
-    }
+  lib_walk_host(grid, (int64_t)a.B * a.n_pieces, [&](int64_t item) {
+    const int32_t b = (int32_t)(item / a.n_pieces);
+    for (int t = 0; t < PK_BLOCK; ++t) merit_thread(a, b, item - (int64_t)b * a.n_pieces, t, s);
+    lib_tree_host(merit_tree_step, s);
+    for (int q = 0; q < PK_MERIT_COLS; ++q) merit_store_partial(a, item, q, s);
+  });
 }
 
 static void merit_fin_host(const PkMeritArgs& a, unsigned grid) {
   double s[PK_MERIT_PLANES * PK_BLOCK];
-  for (unsigned wg = 0; wg < grid; ++wg)
-    for (int32_t b = (int32_t)wg; b < a.B; b += (int32_t)grid) {
-      for (int t = 0; t < PK_BLOCK; ++t) merit_fin_thread(a, b, t, s);
-      merit_tree_host(s);
-      for (int q = 0; q < PK_MERIT_COLS; ++q) merit_store_out(a, b, q, s);
-    }
+  lib_walk_host(grid, a.B, [&](int64_t b) {
+    for (int t = 0; t < PK_BLOCK; ++t) merit_fin_thread(a, (int32_t)b, t, s);
+    lib_tree_host(merit_tree_step, s);
+    for (int q = 0; q < PK_MERIT_COLS; ++q) merit_store_out(a, (int32_t)b, q, s);
+  });
 }
 
 static void trial_host(const PkTrialArgs& a, unsigned grid) {
-  for (unsigned wg = 0; wg < grid; ++wg)
-    for (int t = 0; t < PK_BLOCK; ++t)
-      for (int64_t i = (int64_t)wg * PK_BLOCK + t; i < a.n; i += (int64_t)grid * PK_BLOCK) trial_element(a, (int32_t)i);
+  lib_walk_host(grid, trial_items(a.n), [&](int64_t item) {
+    for (int64_t i = item * PK_BLOCK; i < std::min<int64_t>(a.n, (item + 1) * PK_BLOCK); ++i) trial_element(a, (int32_t)i);
+  });
 }
 #endif
 
-// The grid rule of the three kernels, stated once (pk_ops.cpp's): one workgroup per work item -- a piece of an entry, an entry,
-// 256 elements of x -- up to PK_MERIT_GRID_CAP (8 workgroups of 256 threads fill a CU's 2048 thread slots, 256 CUs), the items
-// beyond it in a stride loop.  A work item's result is a function of the item alone: it does not depend on the cap.
-enum { PK_MERIT_GRID_CAP = 2048 };
-static unsigned merit_grid(int64_t items) { return (unsigned)std::min<int64_t>(items, PK_MERIT_GRID_CAP); }
+// The work items of the grid rule (lib_grid, pk_libkernel.h): a piece of an entry (pk_merit), an entry (pk_merit_fin), 256
+// elements of x (pk_trial).
 
 static int64_t merit_pieces(int64_t n_g, int64_t n_x) {
   return std::max<int64_t>(1, (std::max(n_g, n_x) + PK_MERIT_PIECE - 1) / PK_MERIT_PIECE);
@@ -365,14 +344,7 @@ int pk_trial_points_dev(pk_ctx* c, int B, const double* d_x, const double* d_d, 
   a.x = d_x; a.d = d_d; a.X = d_X; a.ldx = ldx; a.n = c->n; a.B = B;
   std::copy(alpha, alpha + B, a.alpha);
   hipStream_t st = pick(c, stream);
-  const unsigned grid = merit_grid(((int64_t)c->n + PK_BLOCK - 1) / PK_BLOCK);
-  if (!grid) return 0;
-#ifdef __HIPCC__
-  hipLaunchKernelGGL(pk_trial, dim3(grid), dim3(PK_BLOCK), 0, st, a);
-  PK_HIP(c, hipGetLastError());
-#else
-  fake_hip_enqueue(st, [a, grid]() { trial_host(a, grid); });
-#endif
+  if (c->n > 0) PK_LIB_LAUNCH(c, pk_trial, trial_host, lib_grid(trial_items(c->n)), st, a);
   return 0;
 }
 
@@ -395,16 +367,8 @@ int pk_merit_reduce_dev(pk_ctx* c, int B, int64_t n_g, const double* d_g, int64_
     return rc;
   a.partial = c->merit.d_partial;
   hipStream_t st = pick(c, stream);
-  const unsigned grid = merit_grid((int64_t)B * a.n_pieces), grid_fin = merit_grid(B);
-#ifdef __HIPCC__
-  hipLaunchKernelGGL(pk_merit, dim3(grid), dim3(PK_BLOCK), 0, st, a);
-  PK_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(pk_merit_fin, dim3(grid_fin), dim3(PK_BLOCK), 0, st, a);
-  PK_HIP(c, hipGetLastError());
-#else
-  fake_hip_enqueue(st, [a, grid]() { merit_host(a, grid); });
-  fake_hip_enqueue(st, [a, grid_fin]() { merit_fin_host(a, grid_fin); });
-#endif
+  PK_LIB_LAUNCH(c, pk_merit, merit_host, lib_grid((int64_t)B * a.n_pieces), st, a);
+  PK_LIB_LAUNCH(c, pk_merit_fin, merit_fin_host, lib_grid(B), st, a);
   return 0;
 }
 

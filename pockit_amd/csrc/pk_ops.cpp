@@ -17,7 +17,7 @@
 // same row blocks in chunks of at most PK_OP_KMAX columns: pk_op_rows_k / pk_op_long_k read the structure and the values once
 // per chunk and keep one LDS plane of products per column.  Column j of Y has exactly the bits of the single product with
 // column j of V: the association per (row, column) is the one above.
-#include "pk_runtime.h"
+#include "pk_libkernel.h"
 
 // ---------------------------------------------------------------- row blocks (host, once per operator)
 int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBlock>& blocks, std::vector<PkOpLong>& longs,
@@ -47,19 +47,14 @@ int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBloc
 }
 
 // ---------------------------------------------------------------- the walk of one block, shared by the kernels and the host stand-in
-#ifdef __HIPCC__
-#define PK_OP_FN __host__ __device__ __forceinline__
-#else
-#define PK_OP_FN inline
-#endif
-
+// (the function macro, the tree's driver, the grid rule, the host walk and the launch are pk_libkernel.h's)
+//
 // LDS slot of product i: one slot of padding behind every 32.  ds_read_b64 serves a wave as two halves of 32 lanes over
 // 64 banks of 4 bytes, i.e. 32 doubles per cycle: lane r of the row sums reads slot (start of row r) + k, a stride of the
 // row length -- 2, 4, 8 ... doubles for rows of equal even length would be 2-, 4-, 8-way conflicts; with the padding lanes
 // r and r + 32 / len land one bank pair further and the half-wave is conflict-free for every power-of-two length up to 32.
 #define PK_OP_LDS (PK_BLOCK + PK_BLOCK / 32)
-static_assert((PK_BLOCK & (PK_BLOCK - 1)) == 0, "the tree of pk_op_rows halves the workgroup");
-PK_OP_FN int op_slot(int i) { return i + (i >> 5); }
+PK_LIB_FN int op_slot(int i) { return i + (i >> 5); }
 
 struct PkOpArgs {
   const PkOpBlock* blocks;
@@ -71,14 +66,14 @@ struct PkOpArgs {
 };
 
 // thread t of a block: its product (0 beyond the block's count)
-PK_OP_FN double op_product(const PkOpArgs& a, const PkOpBlock& b, int t) {
+PK_LIB_FN double op_product(const PkOpArgs& a, const PkOpBlock& b, int t) {
   if (t >= b.count) return 0.0;
   const int32_t e = b.e0 + t;
   return a.vals[a.src ? a.src[e] : e] * a.v[a.indices[e]];
 }
 
 // thread r < n_rows of a stream block: the products of its row in ascending entry order
-PK_OP_FN void op_row_sum(const PkOpArgs& a, const PkOpBlock& b, int r, const double* s) {
+PK_LIB_FN void op_row_sum(const PkOpArgs& a, const PkOpBlock& b, int r, const double* s) {
   const int32_t row = b.row0 + r;
   const int lo = a.indptr[row] - b.e0, hi = a.indptr[row + 1] - b.e0;
   double sum = 0.0;
@@ -87,14 +82,14 @@ PK_OP_FN void op_row_sum(const PkOpArgs& a, const PkOpBlock& b, int r, const dou
 }
 
 // thread t of a long row: its partial sums first + t, first + t + 256, ... in ascending order
-PK_OP_FN double op_long_strided(const PkOpArgs& a, const PkOpLong& l, int t) {
+PK_LIB_FN double op_long_strided(const PkOpArgs& a, const PkOpLong& l, int t) {
   double sum = 0.0;
   for (int32_t k = t; k < l.pieces; k += PK_BLOCK) sum += a.partial[l.first + k];
   return sum;
 }
 
-// one step of the fixed tree over the 256 slots: widths 128, 64 ... 1
-PK_OP_FN void op_tree_step(double* s, int w, int t) {
+// one step of the fixed tree over the 256 slots (lib_tree: widths 128, 64 ... 1; the sum ends in s[0])
+PK_LIB_FN void op_tree_step(double* s, int w, int t) {
   if (t < w) s[op_slot(t)] += s[op_slot(t + w)];
 }
 
@@ -111,7 +106,7 @@ struct PkOpArgsK {
 };
 
 // two doubles from a 16-byte aligned address: one 16-byte load
-PK_OP_FN void op_load_pair(const double* p, double& x, double& y) {
+PK_LIB_FN void op_load_pair(const double* p, double& x, double& y) {
   double q[2];
   __builtin_memcpy(q, __builtin_assume_aligned(p, 16), sizeof q);
   x = q[0];
@@ -119,7 +114,7 @@ PK_OP_FN void op_load_pair(const double* p, double& x, double& y) {
 }
 
 // thread t of a block: its kc products into the planes (0 beyond the block's count); value, column and src are read once
-PK_OP_FN void op_products_k(const PkOpArgsK& k, const PkOpBlock& b, int t, double* s) {
+PK_LIB_FN void op_products_k(const PkOpArgsK& k, const PkOpBlock& b, int t, double* s) {
   const PkOpArgs& a = k.a;
   double* p = s + op_slot(t);
   if (t >= b.count) {
@@ -143,7 +138,7 @@ PK_OP_FN void op_products_k(const PkOpArgsK& k, const PkOpBlock& b, int t, doubl
 // thread t of a stream block: the n_rows x kc sums are spread over the workgroup, PK_BLOCK / n_rows columns side by side --
 // thread q * n_rows + r takes row r in the columns q, q + PK_BLOCK / n_rows, ... -- each the products of its row in its plane
 // in ascending entry order.  Every (row, column) has one writer, which reads add first.
-PK_OP_FN void op_row_sums_k(const PkOpArgsK& k, const PkOpBlock& b, int t, const double* s) {
+PK_LIB_FN void op_row_sums_k(const PkOpArgsK& k, const PkOpBlock& b, int t, const double* s) {
   const PkOpArgs& a = k.a;
   if (b.n_rows <= 0) return;
   const int step = PK_BLOCK / b.n_rows, q = t / b.n_rows, r = t - q * b.n_rows;
@@ -160,7 +155,7 @@ PK_OP_FN void op_row_sums_k(const PkOpArgsK& k, const PkOpBlock& b, int t, const
 }
 
 // thread t of a long row: per column its partial sums first + t, first + t + 256, ... in ascending order
-PK_OP_FN void op_long_strided_k(const PkOpArgsK& k, const PkOpLong& l, int t, double* s) {
+PK_LIB_FN void op_long_strided_k(const PkOpArgsK& k, const PkOpLong& l, int t, double* s) {
   for (int c = 0; c < k.kc; ++c) {
     double sum = 0.0;
     for (int32_t j = t; j < l.pieces; j += PK_BLOCK) sum += k.a.partial[(int64_t)(l.first + j) * PK_OP_KMAX + c];
@@ -169,7 +164,7 @@ PK_OP_FN void op_long_strided_k(const PkOpArgsK& k, const PkOpLong& l, int t, do
 }
 
 // one step of the kc trees, which share the barrier of the level: the PK_BLOCK / w groups of w threads take a column each
-PK_OP_FN void op_tree_step_k(double* s, int w, int t, int kc) {
+PK_LIB_FN void op_tree_step_k(double* s, int w, int t, int kc) {
   const int i = t & (w - 1);
   for (int c = t / w; c < kc; c += PK_BLOCK / w) {
     double* p = s + c * PK_OP_LDS;
@@ -178,10 +173,10 @@ PK_OP_FN void op_tree_step_k(double* s, int w, int t, int kc) {
 }
 
 // thread t < kc behind the trees: the sum of column t
-PK_OP_FN void op_store_partial_k(const PkOpArgsK& k, const PkOpBlock& b, int t, const double* s) {
+PK_LIB_FN void op_store_partial_k(const PkOpArgsK& k, const PkOpBlock& b, int t, const double* s) {
   k.a.partial[(int64_t)b.row0 * PK_OP_KMAX + t] = s[t * PK_OP_LDS];
 }
-PK_OP_FN void op_store_long_k(const PkOpArgsK& k, const PkOpLong& l, int t, const double* s) {
+PK_LIB_FN void op_store_long_k(const PkOpArgsK& k, const PkOpLong& l, int t, const double* s) {
   const int64_t at = (int64_t)l.row * k.ldy + t;
   const double sum = s[t * PK_OP_LDS];
   k.a.y[at] = k.a.add ? sum + k.a.add[at] : sum;
@@ -189,14 +184,6 @@ PK_OP_FN void op_store_long_k(const PkOpArgsK& k, const PkOpLong& l, int t, cons
 
 #ifdef __HIPCC__
 // ---------------------------------------------------------------- kernels (gfx950)
-__device__ __forceinline__ double op_tree(double* s, int t) {      // (every thread of the workgroup; returns the sum to all)
-  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1) {
-    op_tree_step(s, w, t);
-    __syncthreads();
-  }
-  return s[0];
-}
-
 __global__ void __launch_bounds__(PK_BLOCK) pk_op_rows(PkOpArgs a) {
   __shared__ double s[PK_OP_LDS];
   const int t = (int)threadIdx.x;
@@ -207,8 +194,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_op_rows(PkOpArgs a) {
     if (b.n_rows >= 0) {      // (uniform over the workgroup)
       if (t < b.n_rows) op_row_sum(a, b, t, s);
     } else {
-      const double sum = op_tree(s, t);
-      if (t == 0) a.partial[b.row0] = sum;
+      lib_tree(op_tree_step, s, t);
+      if (t == 0) a.partial[b.row0] = s[0];
     }
     __syncthreads();          // the next block of this workgroup's stride overwrites the slots
   }
@@ -221,15 +208,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_op_long(PkOpArgs a) {
     const PkOpLong l = a.longs[i];
     s[op_slot(t)] = op_long_strided(a, l, t);
     __syncthreads();
-    const double sum = op_tree(s, t);
-    if (t == 0) a.y[l.row] = a.add ? sum + a.add[l.row] : sum;
-    __syncthreads();
-  }
-}
-__device__ __forceinline__ void op_tree_k(double* s, int t, int kc) {      // (every thread of the workgroup; column c ends in s[c * PK_OP_LDS])
-#pragma unroll
-  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1) {
-    op_tree_step_k(s, w, t, kc);
+    lib_tree(op_tree_step, s, t);
+    if (t == 0) a.y[l.row] = a.add ? s[0] + a.add[l.row] : s[0];
     __syncthreads();
   }
 }
@@ -244,7 +224,7 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_op_rows_k(PkOpArgsK k) {
     if (b.n_rows >= 0) {      // (uniform over the workgroup)
       op_row_sums_k(k, b, t, s);
     } else {
-      op_tree_k(s, t, k.kc);
+      lib_tree(op_tree_step_k, s, t, k.kc);      // (column c ends in s[c * PK_OP_LDS])
       if (t < k.kc) op_store_partial_k(k, b, t, s);
     }
     __syncthreads();          // the next block of this workgroup's stride overwrites the planes
@@ -258,82 +238,63 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_op_long_k(PkOpArgsK k) {
     const PkOpLong l = k.a.longs[i];
     op_long_strided_k(k, l, t, s);
     __syncthreads();
-    op_tree_k(s, t, k.kc);
+    lib_tree(op_tree_step_k, s, t, k.kc);      // (column c ends in s[c * PK_OP_LDS])
     if (t < k.kc) op_store_long_k(k, l, t, s);
     __syncthreads();
   }
 }
 #else
 // ---------------------------------------------------------------- host stand-in: the identical walk over the same tables
-static void op_tree_host(double* s) {
-  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1)
-    for (int t = 0; t < PK_BLOCK; ++t) op_tree_step(s, w, t);
-}
-
 static void op_rows_host(const PkOpArgs& a, unsigned grid) {
   double s[PK_OP_LDS];
-  for (unsigned wg = 0; wg < grid; ++wg)
-    for (int32_t i = (int32_t)wg; i < a.n_blocks; i += (int32_t)grid) {
-      const PkOpBlock b = a.blocks[i];
-      for (int t = 0; t < PK_BLOCK; ++t) s[op_slot(t)] = op_product(a, b, t);
-      if (b.n_rows >= 0) {
-        for (int t = 0; t < b.n_rows; ++t) op_row_sum(a, b, t, s);
-      } else {
-        op_tree_host(s);
-        a.partial[b.row0] = s[0];
-      }
+  lib_walk_host(grid, a.n_blocks, [&](int64_t i) {
+    const PkOpBlock b = a.blocks[i];
+    for (int t = 0; t < PK_BLOCK; ++t) s[op_slot(t)] = op_product(a, b, t);
+    if (b.n_rows >= 0) {
+      for (int t = 0; t < b.n_rows; ++t) op_row_sum(a, b, t, s);
+    } else {
+      lib_tree_host(op_tree_step, s);
+      a.partial[b.row0] = s[0];
     }
+  });
 }
 
 static void op_long_host(const PkOpArgs& a, unsigned grid) {
   double s[PK_OP_LDS];
-  for (unsigned wg = 0; wg < grid; ++wg)
-    for (int32_t i = (int32_t)wg; i < a.n_longs; i += (int32_t)grid) {
-      const PkOpLong l = a.longs[i];
-      for (int t = 0; t < PK_BLOCK; ++t) s[op_slot(t)] = op_long_strided(a, l, t);
-      op_tree_host(s);
-      a.y[l.row] = a.add ? s[0] + a.add[l.row] : s[0];
-    }
-}
-
-static void op_tree_k_host(double* s, int kc) {
-  for (int w = PK_BLOCK / 2; w >= 1; w >>= 1)
-    for (int t = 0; t < PK_BLOCK; ++t) op_tree_step_k(s, w, t, kc);
+  lib_walk_host(grid, a.n_longs, [&](int64_t i) {
+    const PkOpLong l = a.longs[i];
+    for (int t = 0; t < PK_BLOCK; ++t) s[op_slot(t)] = op_long_strided(a, l, t);
+    lib_tree_host(op_tree_step, s);
+    a.y[l.row] = a.add ? s[0] + a.add[l.row] : s[0];
+  });
 }
 
 static void op_rows_k_host(const PkOpArgsK& k, unsigned grid) {
   std::vector<double> planes((size_t)PK_OP_KMAX * PK_OP_LDS);
   double* s = planes.data();
-  for (unsigned wg = 0; wg < grid; ++wg)
-    for (int32_t i = (int32_t)wg; i < k.a.n_blocks; i += (int32_t)grid) {
-      const PkOpBlock b = k.a.blocks[i];
-      for (int t = 0; t < PK_BLOCK; ++t) op_products_k(k, b, t, s);
-      if (b.n_rows >= 0) {
-        for (int t = 0; t < PK_BLOCK; ++t) op_row_sums_k(k, b, t, s);
-      } else {
-        op_tree_k_host(s, k.kc);
-        for (int t = 0; t < k.kc; ++t) op_store_partial_k(k, b, t, s);
-      }
+  lib_walk_host(grid, k.a.n_blocks, [&](int64_t i) {
+    const PkOpBlock b = k.a.blocks[i];
+    for (int t = 0; t < PK_BLOCK; ++t) op_products_k(k, b, t, s);
+    if (b.n_rows >= 0) {
+      for (int t = 0; t < PK_BLOCK; ++t) op_row_sums_k(k, b, t, s);
+    } else {
+      lib_tree_host(op_tree_step_k, s, k.kc);
+      for (int t = 0; t < k.kc; ++t) op_store_partial_k(k, b, t, s);
     }
+  });
 }
 
 static void op_long_k_host(const PkOpArgsK& k, unsigned grid) {
   std::vector<double> planes((size_t)PK_OP_KMAX * PK_OP_LDS);
   double* s = planes.data();
-  for (unsigned wg = 0; wg < grid; ++wg)
-    for (int32_t i = (int32_t)wg; i < k.a.n_longs; i += (int32_t)grid) {
-      const PkOpLong l = k.a.longs[i];
-      for (int t = 0; t < PK_BLOCK; ++t) op_long_strided_k(k, l, t, s);
-      op_tree_k_host(s, k.kc);
-      for (int t = 0; t < k.kc; ++t) op_store_long_k(k, l, t, s);
-    }
+  lib_walk_host(grid, k.a.n_longs, [&](int64_t i) {
+    const PkOpLong l = k.a.longs[i];
+    for (int t = 0; t < PK_BLOCK; ++t) op_long_strided_k(k, l, t, s);
+    lib_tree_host(op_tree_step_k, s, k.kc);
+    for (int t = 0; t < k.kc; ++t) op_store_long_k(k, l, t, s);
+  });
 }
 #endif
-
-// The grid rule of both kernels, stated once: one workgroup per work item up to PK_OP_GRID_CAP (8 workgroups of 256 threads
-// fill a CU's 2048 thread slots, 256 CUs), the items beyond it in a stride loop -- the result does not depend on it.
-enum { PK_OP_GRID_CAP = 2048 };
-static unsigned op_grid(int32_t items) { return (unsigned)std::min<int32_t>(items, PK_OP_GRID_CAP); }
 
 static void free_operator(PkOperator& o) {
   release(o.d_indptr); release(o.d_indices); release(o.d_src); release(o.d_blocks); release(o.d_longs); release(o.d_partial);
@@ -349,6 +310,22 @@ void free_operators(pk_ctx* c) {
 }
 
 void drop_linearization(pk_ctx* c) { c->ops.lin_J = c->ops.lin_H = nullptr; }
+
+// The entry checks of the four pk_apply_operator* entry points, in the order they fire; ``who`` is the name in the message.
+static int op_ready(pk_ctx* c, int op, bool pointers, const char* who) {
+  if (op < 0 || op > 2) return fail(c, 110, "%s: op must be 0 (J), 1 (J^T) or 2 (H symmetric)", who);
+  if (c->ops.op[op].n_blocks == 0) return fail(c, 117, "%s: call pk_set_csr_operator(%d) first", who, op);
+  if (!pointers) return fail(c, 110, "%s: null device pointer", who);
+  return 0;
+}
+
+// ... and of the two host forms behind it: the value array pk_linearize left for this operator
+static int op_linearized(pk_ctx* c, int op, const double*& vals, const char* who) {
+  vals = op == 2 ? c->ops.lin_H : c->ops.lin_J;
+  if (!vals && op == 2 && c->ops.lin_J) return fail(c, 118, "%s: the linearization has no Hessian (pk_linearize without lambda)", who);
+  if (!vals) return fail(c, 118, "%s: no linearization (pk_linearize)", who);
+  return 0;
+}
 
 extern "C" {
 
@@ -407,39 +384,23 @@ int pk_set_csr_operator(pk_ctx* c, int op, const int32_t* indptr, const int32_t*
 int pk_apply_operator_dev(pk_ctx* c, int op, const double* d_vals, const double* d_v, const double* d_add, double* d_y,
                           void* stream) {
   int rc = ready(c);
-  if (rc) return rc;
-  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  if (rc || (rc = op_ready(c, op, d_vals && d_v && d_y, "pk_apply_operator"))) return rc;
   const PkOperator& o = c->ops.op[op];
-  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator: call pk_set_csr_operator(%d) first", op);
-  if (!d_vals || !d_v || !d_y) return fail(c, 110, "pk_apply_operator: null device pointer");
   PkOpArgs a{};
   a.blocks = o.d_blocks; a.longs = o.d_longs; a.indptr = o.d_indptr; a.indices = o.d_indices; a.src = o.d_src;
   a.vals = d_vals; a.v = d_v; a.add = d_add; a.y = d_y; a.partial = o.d_partial;
   a.n_blocks = o.n_blocks; a.n_longs = o.n_longs;
   hipStream_t st = pick(c, stream);
-  const unsigned grid = op_grid(o.n_blocks), grid_long = op_grid(o.n_longs);
-#ifdef __HIPCC__
-  hipLaunchKernelGGL(pk_op_rows, dim3(grid), dim3(PK_BLOCK), 0, st, a);
-  PK_HIP(c, hipGetLastError());
-  if (grid_long) {
-    hipLaunchKernelGGL(pk_op_long, dim3(grid_long), dim3(PK_BLOCK), 0, st, a);
-    PK_HIP(c, hipGetLastError());
-  }
-#else
-  fake_hip_enqueue(st, [a, grid]() { op_rows_host(a, grid); });
-  if (grid_long) fake_hip_enqueue(st, [a, grid_long]() { op_long_host(a, grid_long); });
-#endif
+  PK_LIB_LAUNCH(c, pk_op_rows, op_rows_host, lib_grid(o.n_blocks), st, a);
+  if (o.n_longs) PK_LIB_LAUNCH(c, pk_op_long, op_long_host, lib_grid(o.n_longs), st, a);
   return 0;
 }
 
 int pk_apply_operator_block_dev(pk_ctx* c, int op, const double* d_vals, int32_t k, const double* d_V, int64_t ldv,
                                 const double* d_Add, double* d_Y, int64_t ldy, void* stream) {
   int rc = ready(c);
-  if (rc) return rc;
-  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator_block: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  if (rc || (rc = op_ready(c, op, d_vals && d_V && d_Y, "pk_apply_operator_block"))) return rc;
   PkOperator& o = c->ops.op[op];
-  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator_block: call pk_set_csr_operator(%d) first", op);
-  if (!d_vals || !d_V || !d_Y) return fail(c, 110, "pk_apply_operator_block: null device pointer");
   if (k < 1) return fail(c, 120, "pk_apply_operator_block: k = %d, a block has at least one column", k);
   if (ldv < k || ldy < k)
     return fail(c, 121, "pk_apply_operator_block: leading dimensions %lld / %lld are smaller than k = %d", (long long)ldv, (long long)ldy, k);
@@ -456,22 +417,12 @@ int pk_apply_operator_block_dev(pk_ctx* c, int op, const double* d_vals, int32_t
   a.a.n_blocks = o.n_blocks; a.a.n_longs = o.n_longs;
   a.ldv = ldv; a.ldy = ldy;
   hipStream_t st = pick(c, stream);
-  const unsigned grid = op_grid(o.n_blocks), grid_long = op_grid(o.n_longs);
   // chunks of PK_OP_KMAX columns, the last one narrower; the launches are ordered by the stream, so they share the partial sums
   for (int32_t c0 = 0; c0 < k; c0 += PK_OP_KMAX) {
     a.kc = std::min<int32_t>(PK_OP_KMAX, k - c0);
     a.a.v = d_V + c0; a.a.add = d_Add ? d_Add + c0 : nullptr; a.a.y = d_Y + c0;
-#ifdef __HIPCC__
-    hipLaunchKernelGGL(pk_op_rows_k, dim3(grid), dim3(PK_BLOCK), 0, st, a);
-    PK_HIP(c, hipGetLastError());
-    if (grid_long) {
-      hipLaunchKernelGGL(pk_op_long_k, dim3(grid_long), dim3(PK_BLOCK), 0, st, a);
-      PK_HIP(c, hipGetLastError());
-    }
-#else
-    fake_hip_enqueue(st, [a, grid]() { op_rows_k_host(a, grid); });
-    if (grid_long) fake_hip_enqueue(st, [a, grid_long]() { op_long_k_host(a, grid_long); });
-#endif
+    PK_LIB_LAUNCH(c, pk_op_rows_k, op_rows_k_host, lib_grid(o.n_blocks), st, a);
+    if (o.n_longs) PK_LIB_LAUNCH(c, pk_op_long_k, op_long_k_host, lib_grid(o.n_longs), st, a);
   }
   return 0;
 }
@@ -494,29 +445,23 @@ int pk_linearize(pk_ctx* c, const double* x, const double* lambda, double sigma)
 }
 
 int pk_apply_operator(pk_ctx* c, int op, const double* v, double* y) {
-  if (const int rc = host_ready(c, v && y)) return rc;
-  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  const double* vals = nullptr;
+  int rc = host_ready(c, v && y);
+  if (rc || (rc = op_ready(c, op, true, "pk_apply_operator")) || (rc = op_linearized(c, op, vals, "pk_apply_operator"))) return rc;
   const PkOperator& o = c->ops.op[op];
-  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator: call pk_set_csr_operator(%d) first", op);
-  const double* vals = op == 2 ? c->ops.lin_H : c->ops.lin_J;
-  if (!vals && op == 2 && c->ops.lin_J) return fail(c, 118, "pk_apply_operator: the linearization has no Hessian (pk_linearize without lambda)");
-  if (!vals) return fail(c, 118, "pk_apply_operator: no linearization (pk_linearize)");
   PK_HIP(c, hipSetDevice(c->device));
   PK_HIP(c, hipMemcpyAsync(c->ops.d_v, v, sizeof(double) * (size_t)o.n_cols, hipMemcpyHostToDevice, c->stream));
-  if (const int rc = pk_apply_operator_dev(c, op, vals, c->ops.d_v, nullptr, c->ops.d_y, nullptr)) return rc;
+  if ((rc = pk_apply_operator_dev(c, op, vals, c->ops.d_v, nullptr, c->ops.d_y, nullptr))) return rc;
   PK_HIP(c, hipMemcpyAsync(y, c->ops.d_y, sizeof(double) * (size_t)o.n_rows, hipMemcpyDeviceToHost, c->stream));
   PK_HIP(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
 int pk_apply_operator_block(pk_ctx* c, int op, int32_t k, const double* V, double* Y) {
-  if (const int rc = host_ready(c, V && Y)) return rc;
-  if (op < 0 || op > 2) return fail(c, 110, "pk_apply_operator_block: op must be 0 (J), 1 (J^T) or 2 (H symmetric)");
+  const double* vals = nullptr;
+  int rc = host_ready(c, V && Y);
+  if (rc || (rc = op_ready(c, op, true, "pk_apply_operator_block")) || (rc = op_linearized(c, op, vals, "pk_apply_operator_block"))) return rc;
   const PkOperator& o = c->ops.op[op];
-  if (o.n_blocks == 0) return fail(c, 117, "pk_apply_operator_block: call pk_set_csr_operator(%d) first", op);
-  const double* vals = op == 2 ? c->ops.lin_H : c->ops.lin_J;
-  if (!vals && op == 2 && c->ops.lin_J) return fail(c, 118, "pk_apply_operator_block: the linearization has no Hessian (pk_linearize without lambda)");
-  if (!vals) return fail(c, 118, "pk_apply_operator_block: no linearization (pk_linearize)");
   if (k < 1) return fail(c, 120, "pk_apply_operator_block: k = %d, a block has at least one column", k);
   PK_HIP(c, hipSetDevice(c->device));
   if (k > c->ops.scratch_k) {      // the scratch grows to the widest block seen and never shrinks short of free_operators
@@ -535,7 +480,7 @@ int pk_apply_operator_block(pk_ctx* c, int op, int32_t k, const double* V, doubl
     c->ops.d_v = v; c->ops.d_y = y; c->ops.scratch_k = k;
   }
   PK_HIP(c, hipMemcpyAsync(c->ops.d_v, V, sizeof(double) * (size_t)o.n_cols * (size_t)k, hipMemcpyHostToDevice, c->stream));
-  if (const int rc = pk_apply_operator_block_dev(c, op, vals, k, c->ops.d_v, k, nullptr, c->ops.d_y, k, nullptr)) return rc;
+  if ((rc = pk_apply_operator_block_dev(c, op, vals, k, c->ops.d_v, k, nullptr, c->ops.d_y, k, nullptr))) return rc;
   PK_HIP(c, hipMemcpyAsync(Y, c->ops.d_y, sizeof(double) * (size_t)o.n_rows * (size_t)k, hipMemcpyDeviceToHost, c->stream));
   PK_HIP(c, hipStreamSynchronize(c->stream));
   return 0;

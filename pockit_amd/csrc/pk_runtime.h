@@ -12,6 +12,9 @@
 //                   own kernels), the bounds they are measured against, the scratch of the host forms
 //   pk_error.cpp    fail(): where an error message is kept
 //
+// pk_libkernel.h, on top of this header, is what pk_ops.cpp and pk_merit.cpp share beyond it: the scaffolding of kernels that
+// are compiled into the library (function macro, tree driver, grid rule, host walk, launch).
+//
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
 // few helpers that cross a unit boundary.  The helpers of the per-callback path are either defined in
 // pk_shim.cpp, beside the callbacks, or inline here.

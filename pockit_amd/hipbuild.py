@@ -52,7 +52,7 @@ RUNTIME_SOURCES = [os.path.join(CSRC, name) for name in
 # (the helper-thread pool and the error slot it reports into: no HIP in either)
 POOL_SOURCES = [os.path.join(CSRC, name) for name in ("pk_pool.cpp", "pk_error.cpp")]
 RUNTIME_HEADERS = [os.path.join(CSRC, name) for name in
-                   ("pk_runtime.h", "pk_error.h", "pockit_hip_internal.h", "pk_abi.h", "pk_launch.h")] + [
+                   ("pk_runtime.h", "pk_libkernel.h", "pk_error.h", "pockit_hip_internal.h", "pk_abi.h", "pk_launch.h")] + [
                        os.path.join(os.path.dirname(HERE), "include", "pockit_hip.h")]
 
 

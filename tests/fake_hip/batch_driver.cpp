@@ -8,23 +8,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pockit_hip.h"
-#include "../../pockit_amd/csrc/pockit_hip_internal.h"
-#include "../../pockit_amd/csrc/pk_abi.h"
+#include "driver_common.h"
 #include "../../pockit_amd/csrc/pk_runtime.h"      // (the context itself: the status words and the hand-off slots of a batch)
-#include "fake_hip.h"
-
-static int g_checks = 0;
-static pk_ctx* ctx = nullptr;
-#define CHECK(cond)                                                                                  \
-  do {                                                                                               \
-    ++g_checks;                                                                                      \
-    if (!(cond)) {                                                                                   \
-      std::fprintf(stderr, "batch_driver.cpp:%d: CHECK failed: %s (%s)\n", __LINE__, #cond, pk_last_error(ctx)); \
-      std::exit(1);                                                                                  \
-    }                                                                                                \
-  } while (0)
-#define OK(call) CHECK((call) == 0)
 
 static std::vector<std::string> ops_since(size_t mark) {
   const auto& lg = fake_hip_log();
@@ -39,7 +24,6 @@ int main() {
   pk_model_desc md{};
   md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
   md.ne_j = md.ne_h = md.ne_a = 1; md.prepass_f = 1; md.tab_cap = 64;
-  const char image[16] = "fake code";
   CHECK(pk_load_batch_model(ctx, image, sizeof image) == 2);      // no model yet
   OK(pk_load_model(ctx, image, sizeof image, &md));
   PkPhase ph{};
@@ -153,6 +137,5 @@ int main() {
   pk_destroy(ctx);
   ctx = nullptr;
   CHECK(fake_hip_live_allocations() == 0);
-  std::printf("%d checks passed\n", g_checks);
-  return 0;
+  return checks_passed();
 }

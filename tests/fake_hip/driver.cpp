@@ -19,35 +19,18 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pockit_hip.h"
-#include "../../pockit_amd/csrc/pockit_hip_internal.h"
-#include "../../pockit_amd/csrc/pk_abi.h"
-#include "fake_hip.h"
-
-static int g_checks = 0;
 static char g_where[256] = "start";
-#define CHECK(cond)                                                                         \
-  do {                                                                                      \
-    ++g_checks;                                                                             \
-    if (!(cond)) {                                                                          \
-      std::fprintf(stderr, "driver.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, g_where);  \
-      { const auto& lg = fake_hip_log(); std::fprintf(stderr, "last operations:");                 \
-        for (size_t i_ = lg.size() > 40 ? lg.size() - 40 : 0; i_ < lg.size(); ++i_) std::fprintf(stderr, " %s", lg[i_].c_str()); \
-        std::fprintf(stderr, "\n"); }                                                             \
-      std::exit(1);                                                                         \
-    }                                                                                       \
-  } while (0)
-#define OK(call)                                                                                        \
-  do {                                                                                                  \
-    int rc_ = (call);                                                                                   \
-    ++g_checks;                                                                                         \
-    if (rc_ != 0) {                                                                                     \
-      std::fprintf(stderr, "driver.cpp:%d: %s -> %d: %s\n", __LINE__, #call, rc_, pk_last_error(ctx));  \
-      std::exit(1);                                                                                     \
-    }                                                                                                   \
-  } while (0)
+static void where_and_last_operations();
+#define CHECK_CONTEXT() where_and_last_operations()
+#include "driver_common.h"
 
-static pk_ctx* ctx = nullptr;
+static void where_and_last_operations() {
+  const auto& lg = fake_hip_log();
+  std::fprintf(stderr, "[%s]\nlast operations:", g_where);
+  for (size_t i = lg.size() > 40 ? lg.size() - 40 : 0; i < lg.size(); ++i) std::fprintf(stderr, " %s", lg[i].c_str());
+  std::fprintf(stderr, "\n");
+}
+
 static FakeSizes S;
 static bool in_runs(const std::vector<std::pair<int64_t, int64_t>>& r, int64_t p) {
   for (auto& q : r)
@@ -120,7 +103,6 @@ static void launch_trace_case(const TraceCase& tc) {
   S = FakeSizes();
   S.n = 37; S.m = 23; S.nnz_J = 600; S.nnz_H = 97; S.nnz_Jc = 150; S.nnz_Hc = 41;
   fake_hip_set_sizes(S);
-  const char image[16] = "fake code";
   OK(pk_create(&ctx, 0));
   OK(pk_load_model(ctx, image, sizeof image, &tc.md));
   PkPhase ph{};
@@ -259,7 +241,6 @@ int main(int argc, char** argv) {
   pk_model_desc md{};
   md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
   md.ne_j = md.ne_h = md.ne_a = md.ne_hc = md.ne_jc = 1; md.prepass_f = 1; md.tab_cap = 64;
-  const char image[16] = "fake code";
   md.tab_cap = 65;
   CHECK(pk_load_model(ctx, image, sizeof image, &md) != 0);    // refused capacity
   md.tab_cap = 64;

@@ -15,27 +15,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pockit_hip.h"
-#include "../../pockit_amd/csrc/pockit_hip_internal.h"
-#include "../../pockit_amd/csrc/pk_abi.h"
+#include "driver_common.h"
 #include "../../pockit_amd/csrc/pk_runtime.h"      // (the context's merit area: d_bounds, partial_cap, scratch_cap)
-#include "fake_hip.h"
-
-static int g_checks = 0;
-static pk_ctx* ctx = nullptr;
-#define CHECK(cond)                                                                                        \
-  do {                                                                                                     \
-    ++g_checks;                                                                                            \
-    if (!(cond)) {                                                                                         \
-      std::fprintf(stderr, "merit_driver.cpp:%d: CHECK failed: %s (%s)\n", __LINE__, #cond, pk_last_error(ctx)); \
-      std::exit(1);                                                                                        \
-    }                                                                                                      \
-  } while (0)
-#define OK(call) CHECK((call) == 0)
 
 static const double INF = std::numeric_limits<double>::infinity();
 static const double NAN_ = std::numeric_limits<double>::quiet_NaN();
-static const double SENTINEL = -77.5;
 
 static double viol(double v, double lo, double hi) { return std::max(std::max(lo - v, v - hi), 0.0); }
 
@@ -73,22 +57,6 @@ static void make_bounds(int64_t len, int salt, std::vector<double>& lo, std::vec
     lo[(size_t)i] = (i + salt) % 7 == 0 ? -INF : small(i + salt, 5, 4);       // -4 ... 0
     hi[(size_t)i] = (i + salt) % 5 == 0 ? INF : small(i + 3 * salt, 4, 0);    //  0 ... 3
   }
-}
-
-static const char image[16] = "fake code";
-static PkPhase g_phase{};
-static PkTile g_tiles[2 * PK_WAVES_PER_BLOCK] = {};
-
-static void set_problem(int32_t n, int32_t m, int64_t nnz_J, int64_t nnz_H) {
-  FakeSizes S;
-  S.n = n; S.m = m; S.nnz_J = nnz_J; S.nnz_H = nnz_H;
-  fake_hip_set_sizes(S);
-  for (auto& t : g_tiles) t.K = 1;
-  g_phase.tile_hi = 2 * PK_WAVES_PER_BLOCK;
-  pk_problem_desc pd{};
-  pd.n = n; pd.m = m; pd.n_phase = 1; pd.nnz_J = nnz_J; pd.nnz_H = nnz_H;
-  pd.phases = &g_phase; pd.tiles = g_tiles; pd.n_tiles = 2 * PK_WAVES_PER_BLOCK;
-  OK(pk_set_problem(ctx, &pd));
 }
 
 // one synthetic reduction through pk_merit_reduce_dev: g of n_g values, X and grad of n_x, B entries, rows padded with NaN
@@ -345,6 +313,5 @@ int main() {
   pk_destroy(ctx);
   ctx = nullptr;
   CHECK(fake_hip_live_allocations() == 0);
-  std::printf("%d checks passed\n", g_checks);
-  return 0;
+  return checks_passed();
 }

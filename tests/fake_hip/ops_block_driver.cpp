@@ -13,65 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pockit_hip.h"
-#include "../../pockit_amd/csrc/pockit_hip_internal.h"
-#include "../../pockit_amd/csrc/pk_abi.h"
+#include "driver_common.h"
 #include "../../pockit_amd/csrc/pk_runtime.h"      // (the context's operator tables: d_partial_k, scratch_k)
-#include "fake_hip.h"
 
-static int g_checks = 0;
-static pk_ctx* ctx = nullptr;
-#define CHECK(cond)                                                                                        \
-  do {                                                                                                     \
-    ++g_checks;                                                                                            \
-    if (!(cond)) {                                                                                         \
-      std::fprintf(stderr, "ops_block_driver.cpp:%d: CHECK failed: %s (%s)\n", __LINE__, #cond, pk_last_error(ctx)); \
-      std::exit(1);                                                                                        \
-    }                                                                                                      \
-  } while (0)
-#define OK(call) CHECK((call) == 0)
-
-struct Csr {
-  int32_t rows = 0, cols = 0;
-  std::vector<int32_t> indptr, indices, src;      // src empty: the identity
-  int64_t nnz() const { return (int64_t)indices.size(); }
-  const int32_t* srcp() const { return src.empty() ? nullptr : src.data(); }
-};
-
-// rows of the given lengths, columns ascending and distinct within a row
-static Csr from_lengths(const std::vector<int32_t>& lens, int32_t cols) {
-  Csr A;
-  A.rows = (int32_t)lens.size(); A.cols = cols;
-  A.indptr.push_back(0);
-  for (int32_t r = 0; r < A.rows; ++r) {
-    const int32_t L = lens[(size_t)r], off = L < cols ? (r * 7) % (cols - L + 1) : 0;
-    if (L > cols) std::exit(2);
-    for (int32_t k = 0; k < L; ++k) A.indices.push_back(off + k);
-    A.indptr.push_back((int32_t)A.indices.size());
-  }
-  return A;
-}
-
-// CSR of the transpose, src pointing into A's values
-static Csr transposed(const Csr& A) {
-  Csr T;
-  T.rows = A.cols; T.cols = A.rows;
-  T.indptr.assign((size_t)T.rows + 1, 0);
-  for (int32_t j : A.indices) ++T.indptr[(size_t)j + 1];
-  for (int32_t j = 0; j < T.rows; ++j) T.indptr[(size_t)j + 1] += T.indptr[(size_t)j];
-  T.indices.resize(A.indices.size()); T.src.resize(A.indices.size());
-  std::vector<int32_t> at(T.indptr.begin(), T.indptr.end() - 1);
-  for (int32_t r = 0; r < A.rows; ++r)
-    for (int32_t e = A.indptr[(size_t)r]; e < A.indptr[(size_t)r + 1]; ++e) {
-      const int32_t q = at[(size_t)A.indices[(size_t)e]]++;
-      T.indices[(size_t)q] = r; T.src[(size_t)q] = e;
-    }
-  return T;
-}
-
-static double small_val(int64_t e) { return (double)((e * 31) % 17 - 8); }
-static double small_vec(int64_t j) { return (double)((j * 13) % 11 - 5); }
-static const double SENTINEL = -77.5;
 
 // a row-major block: rows x k in a buffer of leading dimension ld, the padding filled with ``pad``
 struct Block {
@@ -112,32 +56,6 @@ static bool equals(const Block& Y, const std::vector<double>& want) {
     for (int32_t j = 0; j < Y.k; ++j)
       if (Y.at(r, j) != want[(size_t)r * (size_t)Y.k + (size_t)j]) return false;
   return true;
-}
-
-static const char image[16] = "fake code";
-static PkPhase g_phase{};
-static PkTile g_tiles[2 * PK_WAVES_PER_BLOCK] = {};
-
-static void set_problem(int32_t n, int32_t m, int64_t nnz_J, int64_t nnz_H) {
-  FakeSizes S;
-  S.n = n; S.m = m; S.nnz_J = nnz_J; S.nnz_H = nnz_H;
-  fake_hip_set_sizes(S);
-  for (auto& t : g_tiles) t.K = 1;
-  g_phase.tile_hi = 2 * PK_WAVES_PER_BLOCK;
-  pk_problem_desc pd{};
-  pd.n = n; pd.m = m; pd.n_phase = 1; pd.nnz_J = nnz_J; pd.nnz_H = nnz_H;
-  pd.phases = &g_phase; pd.tiles = g_tiles; pd.n_tiles = 2 * PK_WAVES_PER_BLOCK;
-  OK(pk_set_problem(ctx, &pd));
-}
-
-static void set_identity_map(int which, int64_t count) {
-  std::vector<int32_t> perm((size_t)count);
-  for (int64_t q = 0; q < count; ++q) perm[(size_t)q] = (int32_t)q;
-  OK(pk_set_csr_map(ctx, which, nullptr, perm.data(), count, count));
-}
-
-static int set_operator(int op, const Csr& A) {
-  return pk_set_csr_operator(ctx, op, A.indptr.data(), A.indices.data(), A.srcp(), A.rows, A.cols, A.nnz());
 }
 
 static const int32_t KS[] = {1, 2, 3, 7, 8, 9, 17};
@@ -338,6 +256,5 @@ int main() {
   pk_destroy(ctx);
   ctx = nullptr;
   CHECK(fake_hip_live_allocations() == 0);
-  std::printf("%d checks passed\n", g_checks);
-  return 0;
+  return checks_passed();
 }

@@ -34,7 +34,7 @@ U = 2.0 ** -53
 BLOCK = 256                 # PK_BLOCK
 PER_THREAD = 8              # PK_MERIT_PER_THREAD
 PIECE = BLOCK * PER_THREAD  # PK_MERIT_PIECE
-GRID_CAP = 2048             # PK_MERIT_GRID_CAP
+GRID_CAP = 2048             # PK_LIB_GRID_CAP of csrc/pk_libkernel.h
 COLUMNS = ("f", "theta1", "theta_inf", "theta2_sq", "bound1", "bound_inf", "slope", "bad")
 SUM_COLUMNS, MAX_COLUMNS = (1, 3, 4, 6), (2, 5)
 SCALES = (-40, -20, 0, 20, 40)

@@ -29,7 +29,7 @@ import numpy as np
 
 U = 2.0 ** -53
 BLOCK = 256                 # PK_BLOCK
-OP_GRID_CAP = 2048          # PK_OP_GRID_CAP of pk_ops.cpp
+OP_GRID_CAP = 2048          # PK_LIB_GRID_CAP of csrc/pk_libkernel.h
 BUCKETS = (-40, -20, 0, 20, 40)
 
 # context -> model and the sizes the cases are built for (both test files assert them against the plan)

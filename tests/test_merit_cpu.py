@@ -14,21 +14,14 @@ from pockit_amd import merit, runtime
 from pockit_amd.evaluator import Evaluator
 from pockit_amd.hipbuild import RUNTIME_SOURCES
 from pockit_amd.model import SystemBase
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAKE = os.path.join(ROOT, "tests", "fake_hip")
+from sanitized_build import sanitized_driver
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_merit_entry_points_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     """A stand-alone program (its own main): nothing sanitized is loaded into Python."""
     assert any(os.path.basename(s) == "pk_merit.cpp" for s in RUNTIME_SOURCES)
-    exe = str(tmp_path / "pk_merit_sanitized")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-           "-fno-sanitize-recover=undefined", "-I", FAKE, "-I", ROOT] + RUNTIME_SOURCES + [
-               os.path.join(FAKE, "fake_hip.cpp"), os.path.join(FAKE, "merit_driver.cpp"), "-o", exe]
-    build = subprocess.run(cmd, capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-4000:]
+    exe = sanitized_driver("merit_driver.cpp", tmp_path)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     run = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])

@@ -9,7 +9,8 @@ import subprocess
 
 import pytest
 
-from pockit_amd.hipbuild import POOL_SOURCES, RUNTIME_SOURCES
+from pockit_amd.hipbuild import POOL_SOURCES
+from sanitized_build import sanitized_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = os.path.join(ROOT, "tests", "fake_hip")
@@ -21,13 +22,7 @@ SANITIZER_ENV = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIO
 @pytest.fixture(scope="module")
 def driver_exe(tmp_path_factory):
     """tests/fake_hip/driver.cpp + the runtime + the stand-in, built once with the address and undefined-behaviour sanitizers."""
-    exe = str(tmp_path_factory.mktemp("runtime") / "pk_runtime_sanitized")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-           "-fno-sanitize-recover=undefined", "-I", FAKE, "-I", ROOT] + RUNTIME_SOURCES + [
-               os.path.join(FAKE, "fake_hip.cpp"), os.path.join(FAKE, "driver.cpp"), "-o", exe]
-    build = subprocess.run(cmd, capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr[-4000:]
-    return exe
+    return sanitized_driver("driver.cpp", tmp_path_factory.mktemp("runtime"))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
