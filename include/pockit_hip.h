@@ -225,6 +225,35 @@ int pk_apply_operator(pk_ctx* ctx, int op, const double* v, double* y);
 int pk_apply_operator_block_dev(pk_ctx* ctx, int op, const double* d_vals, int32_t k, const double* d_V, int64_t ldv,
                                 const double* d_Add, double* d_Y, int64_t ldy, void* stream);
 int pk_apply_operator_block(pk_ctx* ctx, int op, int32_t k, const double* V, double* Y);
+/* What a solver needs about the ENTRIES of the same operators, not about a product (kernels pk_red_rows, pk_red_long, pk_diag of
+ * the library): a reduction over the rows of operator op with a_e = vals[src ? src[e] : e], c_e = indices[e], an optional
+ * weight d_w (n_cols values; NULL: the weight is left out, not multiplied by 1.0) and an optional d_add (n_rows values, may
+ * alias d_y):
+ *   mode 0 abs_sum   t_e = fabs(a_e) * w[c_e]                                     y[row] = sum_e t_e (+ add[row])
+ *   mode 1 sq_sum    t_e = (a_e * a_e) * w[c_e], the square rounded first         y[row] = sum_e t_e (+ add[row])
+ *   mode 2 abs_max   t_e = fabs(a_e) * w[c_e]                                     y[row] = max(0, max_e t_e, add[row])
+ * Row norms of J: op 0; column norms of J: op 1; diag(J D J^T): op 0, mode 1, w = d; diag(J^T D J): op 1, mode 1, w = d.  The
+ * two sums have exactly the association of pk_apply_operator_dev over the same row blocks (no atomics, no dependence on the
+ * grid, the same bits from run to run) and share its partial-sum slots, ordered by the stream.  Mode 2 walks the same way
+ * but takes maxima by comparison (m = 0.0; if (t > m) m = t;): a NaN term loses, the zero padding is the identity, the
+ * result is never negative and never -0.0, and a negative weight gives what the arithmetic gives.  NaN is not screened for.
+ * The diagonal of H: y[i] = pos[i] >= 0 ? vals[pos[i]] : 0.0 (+ add[i]); pk_set_operator_diagonal (op must be 2) uploads pos
+ * once -- n int32 entries pointing into the CSR value array of the Hessian map (pk_set_csr_map(1)), -1 for a row without a
+ * diagonal entry -- after checking it on the host and waiting for the device (a diagonal enqueued earlier on any stream may
+ * still read the old positions); pk_set_csr_map and pk_set_problem drop it with the operators.
+ * The host forms work on the context's linearization (pk_linearize): pk_operator_reduce sends w up (NULL: none) and brings y
+ * down; add_diagonal != 0 (op 1 or 2) computes diag(H) on the device first and reduces with add aliasing y, one round trip
+ * for diag(H + J^T D J).  Errors: 110 op out of range or a null pointer; 117 no operator; 118 no linearization, or none of
+ * H; 119 a sharded context; 111 no Hessian map; 129 mode out of range; 130 a diagonal asked of an operator that is not
+ * square (op 0 or 1), or added to rows that are not H's; 131 pos of the wrong length or with an entry that is neither -1
+ * nor in [0, n_unique); 132 a diagonal before pk_set_operator_diagonal.  Nothing is enqueued after a refusal. */
+int pk_operator_reduce_dev(pk_ctx* ctx, int op, int mode, const double* d_vals, const double* d_w /* or NULL */,
+                           const double* d_add /* or NULL */, double* d_y, void* stream);
+int pk_operator_reduce(pk_ctx* ctx, int op, int mode, const double* w /* or NULL */, int add_diagonal, double* y);
+int pk_set_operator_diagonal(pk_ctx* ctx, int op, const int32_t* pos, int32_t n);
+int pk_operator_diagonal_dev(pk_ctx* ctx, int op, const double* d_vals, const double* d_add /* or NULL */, double* d_y,
+                             void* stream);
+int pk_operator_diagonal(pk_ctx* ctx, int op, double* y);
 
 /* device-pointer API: enqueue on ``stream`` (hipStream_t, NULL = context stream), no sync */
 int pk_eval_f_dev(pk_ctx* ctx, const double* d_x, double* d_f, void* stream);

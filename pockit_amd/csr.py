@@ -6,6 +6,8 @@ here; per iterate the device only gathers (``pk_csr``): ``csr[p] = sum(triplets[
 
 ``CsrOperator``: the structures of the products ``J v``, ``J^T y``, ``H v`` on those values where they lie
 (``csrc/pk_ops.cpp``), built from a map: the matrix itself, its transpose and the symmetric completion of a lower triangle.
+The reductions over their entries (``csrc/pk_reduce.cpp``: row norms, weighted diagonals) walk the same structures; the diagonal
+of H reads ``CsrMap.diagonal_src``.
 """
 from __future__ import annotations
 
@@ -88,6 +90,23 @@ class CsrMap:
         order = np.argsort(r * n_cols + c, kind="stable")      # (no position repeats: L has one entry per position)
         indptr = np.searchsorted(r[order], np.arange(n_rows + 1))
         return CsrOperator(self.shape, indptr, c[order], src[order])
+
+    def diagonal_src(self):
+        """For a lower-triangular map: per row the position of its diagonal entry in this map's values, -1 where the row has
+        none (int32, ``n`` entries).  Columns ascend and never exceed the row, so the diagonal entry is the last entry of a row
+        whose column equals the row.  What ``pk_set_operator_diagonal`` takes."""
+        n_rows, n_cols = self.shape
+        if n_rows != n_cols:
+            raise ValueError("diagonal_src(): the map is not square")
+        rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(self.indptr))
+        if np.any(self.indices > rows):
+            raise ValueError("diagonal_src(): the map has an entry above the diagonal")
+        pos = np.full(n_rows, -1, dtype=np.int32)
+        last = self.indptr[1:].astype(np.int64) - 1
+        live = np.flatnonzero(np.diff(self.indptr) > 0)
+        hit = live[self.indices[last[live]] == live]
+        pos[hit] = last[hit]
+        return pos
 
 
 class CsrOperator:

@@ -17,7 +17,7 @@
 // same row blocks in chunks of at most PK_OP_KMAX columns: pk_op_rows_k / pk_op_long_k read the structure and the values once
 // per chunk and keep one LDS plane of products per column.  Column j of Y has exactly the bits of the single product with
 // column j of V: the association per (row, column) is the one above.
-#include "pk_libkernel.h"
+#include "pk_oprows.h"
 
 // ---------------------------------------------------------------- row blocks (host, once per operator)
 int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBlock>& blocks, std::vector<PkOpLong>& longs,
@@ -47,15 +47,8 @@ int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBloc
 }
 
 // ---------------------------------------------------------------- the walk of one block, shared by the kernels and the host stand-in
-// (the function macro, the tree's driver, the grid rule, the host walk and the launch are pk_libkernel.h's)
-//
-// LDS slot of product i: one slot of padding behind every 32.  ds_read_b64 serves a wave as two halves of 32 lanes over
-// 64 banks of 4 bytes, i.e. 32 doubles per cycle: lane r of the row sums reads slot (start of row r) + k, a stride of the
-// row length -- 2, 4, 8 ... doubles for rows of equal even length would be 2-, 4-, 8-way conflicts; with the padding lanes
-// r and r + 32 / len land one bank pair further and the half-wave is conflict-free for every power-of-two length up to 32.
-#define PK_OP_LDS (PK_BLOCK + PK_BLOCK / 32)
-PK_LIB_FN int op_slot(int i) { return i + (i >> 5); }
-
+// (the function macro, the tree's driver, the grid rule, the host walk and the launch are pk_libkernel.h's; the padded LDS
+// slots, PK_OP_LDS and op_slot, are pk_oprows.h's, shared with the reductions of pk_reduce.cpp)
 struct PkOpArgs {
   const PkOpBlock* blocks;
   const PkOpLong* longs;
@@ -304,23 +297,24 @@ static void free_operator(PkOperator& o) {
 
 void free_operators(pk_ctx* c) {
   for (auto& o : c->ops.op) free_operator(o);
-  release(c->ops.d_v); release(c->ops.d_y);
+  release(c->ops.d_v); release(c->ops.d_y); release(c->ops.d_diag_pos);
   c->ops.scratch_k = 0;
   c->ops.lin_J = c->ops.lin_H = nullptr;
 }
 
 void drop_linearization(pk_ctx* c) { c->ops.lin_J = c->ops.lin_H = nullptr; }
 
-// The entry checks of the four pk_apply_operator* entry points, in the order they fire; ``who`` is the name in the message.
-static int op_ready(pk_ctx* c, int op, bool pointers, const char* who) {
+// The entry checks of the pk_apply_operator* and pk_operator_reduce* entry points, in the order they fire; ``who`` is the name
+// in the message.
+int op_ready(pk_ctx* c, int op, bool pointers, const char* who) {
   if (op < 0 || op > 2) return fail(c, 110, "%s: op must be 0 (J), 1 (J^T) or 2 (H symmetric)", who);
   if (c->ops.op[op].n_blocks == 0) return fail(c, 117, "%s: call pk_set_csr_operator(%d) first", who, op);
   if (!pointers) return fail(c, 110, "%s: null device pointer", who);
   return 0;
 }
 
-// ... and of the two host forms behind it: the value array pk_linearize left for this operator
-static int op_linearized(pk_ctx* c, int op, const double*& vals, const char* who) {
+// ... and of the host forms behind it: the value array pk_linearize left for this operator
+int op_linearized(pk_ctx* c, int op, const double*& vals, const char* who) {
   vals = op == 2 ? c->ops.lin_H : c->ops.lin_J;
   if (!vals && op == 2 && c->ops.lin_J) return fail(c, 118, "%s: the linearization has no Hessian (pk_linearize without lambda)", who);
   if (!vals) return fail(c, 118, "%s: no linearization (pk_linearize)", who);

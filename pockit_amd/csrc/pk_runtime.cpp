@@ -2,7 +2,7 @@
 //
 // This file is the CORE unit: context, model and problem set-up, the launch machinery, the device-pointer entry points, the
 // one-shot host-buffer entry points and the cycle.  Its siblings (pk_runtime.h lists them): pk_shim.cpp (host shim),
-// pk_pool.cpp (helper threads), pk_shard.cpp (sharding), pk_extras.cpp (CSR, mesh error, profiling), pk_ops.cpp (J, J^T, H times a vector), pk_error.cpp.
+// pk_pool.cpp (helper threads), pk_shard.cpp (sharding), pk_extras.cpp (CSR, mesh error, profiling), pk_ops.cpp (J, J^T, H times a vector), pk_reduce.cpp (reductions over their rows), pk_error.cpp.
 //
 // Owns: the HIP context objects of one GPU (stream, loaded code object, kernel handles), the
 // device copies of the per-(model, mesh) tables, and device work buffers (x, lambda, outputs,

@@ -8,11 +8,13 @@
 //   pk_extras.cpp   CSR hand-off, mesh error estimation, profiling and developer tracing
 //   pk_ops.cpp      J, J^T and the symmetric H applied to vectors and blocks of vectors on the device (pk_op_rows, pk_op_long,
 //                   pk_op_rows_k, pk_op_long_k: the library's own kernels)
+//   pk_reduce.cpp   row norms and weighted diagonals of J, J^T and H over the same row blocks, the diagonal of H (pk_red_rows,
+//                   pk_red_long, pk_diag: the library's own kernels)
 //   pk_merit.cpp    merit terms of a batch of trial points reduced on the device (pk_trial, pk_merit, pk_merit_fin: the library's
 //                   own kernels), the bounds they are measured against, the scratch of the host forms
 //   pk_error.cpp    fail(): where an error message is kept
 //
-// pk_libkernel.h, on top of this header, is what pk_ops.cpp and pk_merit.cpp share beyond it: the scaffolding of kernels that
+// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp and pk_merit.cpp share beyond it: the scaffolding of kernels that
 // are compiled into the library (function macro, tree driver, grid rule, host walk, launch).
 //
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
@@ -147,6 +149,8 @@ struct PkOps {
   double *d_v = nullptr, *d_y = nullptr;     // scratch of pk_apply_operator[_block], max(n, m) * scratch_k doubles each
   int64_t scratch_k = 0;                     // columns they hold (1 from pk_set_csr_operator; pk_apply_operator_block grows them)
   const double *lin_J = nullptr, *lin_H = nullptr;   // the linearization of pk_linearize: CSR value arrays of the maps (NULL: none)
+  int32_t* d_diag_pos = nullptr;             // pk_set_operator_diagonal: per row of H its diagonal entry in the Hessian map's CSR
+                                             // values, -1 where there is none (n entries; NULL: not set; pk_reduce.cpp)
 };
 
 // ---- merit terms of a batch of trial points (pk_merit.cpp: pk_set_bounds, pk_merit_batch_dev, pk_merit_scan ...; free_merit)
@@ -391,6 +395,10 @@ void drop_linearization(pk_ctx* c);  // the CSR value arrays of the maps are abo
 // row with more than PK_BLOCK entries, and the list of those long rows.  Pure; nonzero: a count does not fit 32 bits.
 int pk_op_row_blocks(const int32_t* indptr, int32_t n_rows, std::vector<PkOpBlock>& blocks, std::vector<PkOpLong>& longs,
                      int32_t& n_slots);
+// The entry checks the operator entry points of pk_ops.cpp and pk_reduce.cpp share (errors 110, 117; 118 and the value array
+// pk_linearize left for the operator): nothing is enqueued behind a nonzero return.
+int op_ready(pk_ctx* c, int op, bool pointers, const char* who);
+int op_linearized(pk_ctx* c, int op, const double*& vals, const char* who);
 
 // ---- pk_merit.cpp
 void free_merit(pk_ctx* c);          // bounds, partial rows and scratch (with the problem)

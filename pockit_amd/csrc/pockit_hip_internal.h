@@ -172,7 +172,7 @@ int pk_copy_runs_dev(pk_ctx* ctx, const int64_t* d_table, int n_chunks, const do
  * poll such words instead of waiting for the other processes to notice that their GPU has finished) */
 int pk_store_word_dev(pk_ctx* ctx, void* d_dst, int64_t value, void* stream);
 
-/* ================================================================================================ Tuning and diagnostics (10) */
+/* ================================================================================================ Tuning and diagnostics (11) */
 /* `count` back-to-back cycles on the same buffers, enqueued by the library (a solver written against the C ABI launches from
  * compiled code; bench.py's timed batches go through this so that no interpreter loop paces the stream).  xchg = 1: every
  * cycle is followed by pk_exchange_sums_dev(d_x, d_xgrad, d_f) -- the two-launch form of a sharded cycle.  No reference

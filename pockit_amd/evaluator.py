@@ -450,6 +450,7 @@ class Evaluator:
         self._err_views = None
         self._csr = {}
         self._ops = {}               # operators uploaded to the context (pk_set_csr_operator): "J", "JT", "H"
+        self._diag_pos = None        # positions of the diagonal of H uploaded to the context (pk_set_operator_diagonal)
         self._lin_gen = 0            # generation of the context's ONE linearization (Linearization handles compare with it)
         self._code = code
         self._views = {}
@@ -467,7 +468,7 @@ class Evaluator:
         plan, lib, h = self.plan, self.ctx.lib, self.ctx.handle
         self.tables = tb
         self._views = {}
-        self._csr, self._ops = {}, {}      # (pk_set_problem frees the maps and the operators of the context)
+        self._csr, self._ops, self._diag_pos = {}, {}, None      # (pk_set_problem frees the maps and the operators of the context)
         self._bounds, self._bounds_up = None, False      # (... and the uploaded bounds of the merit terms)
         self._lin_gen += 1
         pd = runtime.ProblemDesc()
@@ -801,7 +802,7 @@ class Evaluator:
             else:
                 m = CsrMap(plan.hess_row, plan.hess_col, (plan.n, plan.n))
             seg = None if m.seg is None else m.seg.ctypes.data_as(runtime.c_int32_p)
-            self._ops = {}          # pk_set_csr_map drops the context's operators and its linearization
+            self._ops, self._diag_pos = {}, None      # pk_set_csr_map drops the context's operators and its linearization
             self._lin_gen += 1
             self.ctx.check(self.ctx.lib.pk_set_csr_map(self.ctx.handle, 0 if which == "jac" else 1, seg,
                                                        m.perm.ctypes.data_as(runtime.c_int32_p), m.nnz, m.n_triplets))
@@ -898,6 +899,43 @@ class Evaluator:
         k = int(k)
         self.ctx.check(self.ctx.lib.pk_apply_operator_block_dev(self.ctx.handle, num, d_vals, k, d_V, k if ldv is None else int(ldv),
                                                                 d_add, d_Y, k if ldy is None else int(ldy), stream))
+
+    REDUCE_MODES = {"abs_sum": 0, "sq_sum": 1, "abs_max": 2}
+
+    def _reduce_mode(self, mode):
+        if mode not in self.REDUCE_MODES:
+            raise ValueError('mode must be "abs_sum", "sq_sum" or "abs_max"')
+        return self.REDUCE_MODES[mode]
+
+    def _operator_diagonal(self):
+        """The positions of the diagonal of H in the Hessian map's values (csr.CsrMap.diagonal_src), uploaded on first use
+        like an operator and dropped with the operators."""
+        if self.src.sharded:
+            raise NotImplementedError("the device-side operators are not offered for a sharded evaluator")
+        m = self.csr_map("hess")      # (first: a new map drops the operators and the positions)
+        if self._diag_pos is None:
+            pos = m.diagonal_src()
+            self.ctx.check(self.ctx.lib.pk_set_operator_diagonal(self.ctx.handle, self.OPERATORS["H"],
+                                                                 pos.ctypes.data_as(runtime.c_int32_p), len(pos)))
+            self._diag_pos = pos
+        return self.OPERATORS["H"]
+
+    def operator_reduce_dev(self, op, mode, d_vals, d_y, d_w=None, d_add=None, stream=None):
+        """A reduction over the rows of ``op`` ("J", "JT", "H") on device pointers, ``mode`` one of "abs_sum"
+        (``y[r] = sum_e |a_e| w[c_e]``), "sq_sum" (``sum_e (a_e a_e) w[c_e]``) and "abs_max" (``max(0, max_e |a_e| w[c_e])``);
+        ``d_w`` (one weight per column) may be None: no weight.  ``d_add`` (added to the sums, a further candidate of the
+        maximum) may alias ``d_y``.  The association is that of ``apply_operator_dev``; enqueued on ``stream``, not waited for."""
+        k = self._operator(op)
+        self.ctx.check(self.ctx.lib.pk_operator_reduce_dev(self.ctx.handle, k, self._reduce_mode(mode), d_vals, d_w, d_add, d_y, stream))
+
+    def operator_diagonal_dev(self, op, d_vals, d_y, d_add=None, stream=None):
+        """``y = diag(H(vals)) (+ add)`` on device pointers; ``op`` must be "H", ``d_vals`` a CSR value array of the Hessian map.
+        ``d_add`` may alias ``d_y``.  Enqueued on ``stream``, not waited for."""
+        if op not in self.OPERATORS:
+            raise ValueError('op must be "J", "JT" or "H"')
+        if op != "H":
+            raise ValueError('only "H" is square: J and JT have no diagonal')
+        self.ctx.check(self.ctx.lib.pk_operator_diagonal_dev(self.ctx.handle, self._operator_diagonal(), d_vals, d_add, d_y, stream))
 
     def linearize(self, x, lagrange=None, obj_factor=1.0):
         """Evaluate J at ``x`` -- and the Hessian of the Lagrangian with ``(lagrange, obj_factor)`` unless ``lagrange`` is
@@ -1319,6 +1357,60 @@ class Linearization:
         if not self.has_hessian:
             raise RuntimeError("this linearization has no Hessian: linearize(x, lagrange, obj_factor)")
         return self._apply("H", v, self.n, self.n)
+
+    # ---- about the entries, not about a product: row norms and weighted diagonals (csrc/pk_reduce.cpp)
+    KINDS = {"1": "abs_sum", "2sq": "sq_sum", "inf": "abs_max"}
+
+    def _check_live(self, need_h):
+        """The evaluator of a handle that is still the context's linearization (and has a Hessian where one is needed)."""
+        ev = self._ev
+        if ev.ctx is None or self._gen != ev._lin_gen:
+            raise RuntimeError("stale linearization: the evaluator has been given another evaluation since (one linearization per context)")
+        if need_h and not self.has_hessian:
+            raise RuntimeError("this linearization has no Hessian: linearize(x, lagrange, obj_factor)")
+        return ev
+
+    def _reduce(self, op, mode, weights, with_h=False):
+        ev = self._check_live(op == "H" or with_h)
+        if op not in ev.OPERATORS:
+            raise ValueError('op must be "J", "JT" or "H"')
+        n_rows, n_cols = {"J": (self.m, self.n), "JT": (self.n, self.m), "H": (self.n, self.n)}[op]
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (n_cols,):
+                raise ValueError(f"the weights must have shape ({n_cols},)")
+        k = ev._operator(op)
+        if with_h:
+            ev._operator_diagonal()
+        y = np.empty(n_rows)
+        ev.ctx.check(ev.ctx.lib.pk_operator_reduce(ev.ctx.handle, k, ev._reduce_mode(mode), None if w is None else runtime.as_dp(w),
+                                                   int(with_h), runtime.as_dp(y)))
+        return y
+
+    def row_norms(self, op, kind, weights=None):
+        """Per row of ``op`` ("J", "JT", "H") the norm ``kind`` of its entries: "1" ``sum |a|``, "2sq" ``sum a^2`` (the SQUARE
+        of the 2-norm), "inf" ``max |a|``; with ``weights`` (one per column) every term is multiplied by its column's weight.
+        The column norms of J are ``row_norms("JT", ...)``."""
+        if kind not in self.KINDS:
+            raise ValueError('kind must be "1", "2sq" or "inf"')
+        return self._reduce(op, self.KINDS[kind], weights)
+
+    def h_diag(self):
+        """The diagonal of the Hessian of the Lagrangian (0.0 where the pattern has no diagonal entry)"""
+        ev = self._check_live(True)
+        y = np.empty(self.n)
+        ev.ctx.check(ev.ctx.lib.pk_operator_diagonal(ev.ctx.handle, ev._operator_diagonal(), runtime.as_dp(y)))
+        return y
+
+    def jdjt_diag(self, d):
+        """The diagonal of ``J diag(d) J^T`` (length m): what preconditions the normal equations"""
+        return self._reduce("J", "sq_sum", d)
+
+    def jtdj_diag(self, d, with_h=False):
+        """The diagonal of ``J^T diag(d) J`` (length n); ``with_h``: of ``H + J^T diag(d) J``, the condensed KKT matrix -- the
+        diagonal of H is formed on the device and the sums are added to it there, one round trip."""
+        return self._reduce("JT", "sq_sum", d, with_h=with_h)
 
     def jacobian_operator(self):
         from scipy.sparse.linalg import LinearOperator

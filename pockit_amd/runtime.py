@@ -103,6 +103,11 @@ PROTOTYPES = {
     "pk_apply_operator": (C.c_int, [vp, C.c_int, dp, dp]),
     "pk_apply_operator_block_dev": (C.c_int, [vp, C.c_int, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, vp]),
     "pk_apply_operator_block": (C.c_int, [vp, C.c_int, C.c_int32, dp, dp]),
+    "pk_operator_reduce_dev": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "pk_operator_reduce": (C.c_int, [vp, C.c_int, C.c_int, dp, C.c_int, dp]),
+    "pk_set_operator_diagonal": (C.c_int, [vp, C.c_int, c_int32_p, C.c_int32]),
+    "pk_operator_diagonal_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+    "pk_operator_diagonal": (C.c_int, [vp, C.c_int, dp]),
     "pk_eval_f_dev": (C.c_int, [vp, vp, vp, vp]),
     "pk_eval_grad_dev": (C.c_int, [vp, vp, vp, vp]),
     "pk_eval_g_dev": (C.c_int, [vp, vp, vp, vp]),
