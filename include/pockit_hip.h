@@ -1,8 +1,8 @@
 /* pockit_hip.h -- C ABI of the MI355X NLP-callback evaluator (libpockit_hip.so).
  *
- * STABLE SURFACE.  The 49 entry points declared here are the contract of the library: what a second host binding for
+ * STABLE SURFACE.  The 60 entry points declared here are the contract of the library: what a second host binding for
  * pockit's evaluator path needs -- life cycle, evaluation on host buffers and on device pointers, the compact layouts, the CSR
- * hand-off and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
+ * hand-off with its operators, reductions and the CG solve on them, batches with their merit terms, and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
  * shim, the sharding transport, the helper threads, tuning switches and diagnostics) is declared in
  * pockit_amd/csrc/pockit_hip_internal.h and may change with the project.
  *
@@ -345,6 +345,42 @@ int pk_merit_batch_dev(pk_ctx* ctx, int B, const double* d_f, const double* d_g,
                        void* stream);
 int pk_merit_scan(pk_ctx* ctx, int64_t B, const double* x, const double* d, const double* alpha /* B */, double* out /* B x 8 */);
 int pk_merit_batch(pk_ctx* ctx, int64_t B, const double* X, int64_t ldx, const double* d /* or NULL */, double* out /* B x 8 */);
+
+/* THE CONDENSED KKT MATRIX AND THE NORMAL EQUATIONS, applied and solved by preconditioned CG where the linearization lies
+ * (kernels pk_cg_init, pk_cg_dot, pk_cg_update, pk_cg_scalar, pk_cg_elem of the library; pk_cg.cpp).
+ *   form 0, primal, size n:  K v = [H v] + J^T (d o (J v)) + s o v     d: m values, s: n values
+ *   form 1, dual, size m:    K v = J (d o (J^T v)) + s o v             d: n values, s: m values; no H
+ * d NULL: D = I, no scaling launch; s NULL: no diagonal term; d_hvals NULL: no H.  The products are pk_apply_operator_dev's with
+ * their association, in the fixed order q = s o v, t = A1 v, t = d o t, q = H v + q, q = A2 t + q; no product is fused with a sum.
+ * pk_condensed_apply_dev enqueues one application y = K v; pk_condensed_apply does it on the values of pk_linearize, one round
+ * trip.  The solve keeps a record of 8 doubles on the device: 0 status (0 running, 1 converged, 2 non-positive curvature,
+ * 3 non-finite scalar), 1 completed iterations, 2 r.r of the recurrence, 3 the threshold tol^2 b.b, 4 r.z, 5 the last p^T K p,
+ * 6 the last alpha, 7 the last beta.  pk_cg_begin_dev takes caller-owned device arrays that stay valid and unchanged until the
+ * solve ends -- d_d, d_s, d_minv -- (a diagonal preconditioner z = minv o r, NULL: none) and d_x0 may be NULL; x is written to
+ * d_x; convergence is r.r <= tol^2 b.b.  pk_cg_advance_dev enqueues iters iterations with no synchronisation; once the status
+ * is not 0 an iteration leaves x and the record untouched, so x, iterations and status do not depend on how many were enqueued
+ * beyond the stop.  pk_cg_record copies the record and synchronises.  One solve per context at a time; pk_set_csr_operator,
+ * pk_set_csr_map and pk_set_problem forget it.  The sums are associated in a fixed way: no atomics, the same bits every run.
+ * pk_solve_condensed is the host form on pk_linearize's values: uploads, the preconditioner -- precond 0 none, 1 Jacobi built
+ * on the device, minv = 1 / |diag K| or 1.0 where that is zero or not finite, 2 the caller's minv -- begin, chunks of
+ * min check_every, remaining iterations each followed by a read of the record until the status is not 0 or maxiter iterations
+ * are done, x down.  Exhaustion is status 4 in the host copy rec.  A status is a result, not an error: the call returns 0.
+ * Errors: those of the products -- 110, 117, 118, 119 -- and 132 Jacobi with H before pk_set_operator_diagonal; 133 form out of
+ * range, or H with form 1; 134 tol negative or not finite, iters, maxiter or check_every below 1, precond out of range;
+ * 135 advance or record without a begin; 136 no device memory; 60 a null host buffer.  Nothing is enqueued after a refusal. */
+int pk_condensed_apply_dev(pk_ctx* ctx, int form, const double* d_jvals, const double* d_hvals /* or NULL */,
+                           const double* d_d /* or NULL */, const double* d_s /* or NULL */, const double* d_v, double* d_y,
+                           void* stream);
+int pk_condensed_apply(pk_ctx* ctx, int form, int with_h, const double* d /* or NULL */, const double* s /* or NULL */,
+                       const double* v, double* y);
+int pk_cg_begin_dev(pk_ctx* ctx, int form, const double* d_jvals, const double* d_hvals /* or NULL */, const double* d_d,
+                    const double* d_s, const double* d_minv /* or NULL */, const double* d_b, const double* d_x0 /* or NULL */,
+                    double* d_x, double tol, void* stream);
+int pk_cg_advance_dev(pk_ctx* ctx, int iters, void* stream);
+int pk_cg_record(pk_ctx* ctx, double* rec /* 8 */);
+int pk_solve_condensed(pk_ctx* ctx, int form, int with_h, const double* d, const double* s, int precond,
+                       const double* minv /* precond 2 */, const double* b, const double* x0 /* or NULL */, double tol, int maxiter,
+                       int check_every, double* x, double* rec /* 8 */);
 
 #ifdef __cplusplus
 }

@@ -12,9 +12,11 @@
 //                   pk_red_long, pk_diag: the library's own kernels)
 //   pk_merit.cpp    merit terms of a batch of trial points reduced on the device (pk_trial, pk_merit, pk_merit_fin: the library's
 //                   own kernels), the bounds they are measured against, the scratch of the host forms
+//   pk_cg.cpp       the condensed KKT matrix and the normal equations applied and solved by preconditioned CG on the device
+//                   (pk_cg_init, pk_cg_dot, pk_cg_update, pk_cg_scalar, pk_cg_elem: the library's own kernels), its work vectors
 //   pk_error.cpp    fail(): where an error message is kept
 //
-// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp and pk_merit.cpp share beyond it: the scaffolding of kernels that
+// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp and pk_cg.cpp share beyond it: the scaffolding of kernels that
 // are compiled into the library (function macro, tree driver, grid rule, host walk, launch).
 //
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
@@ -160,6 +162,25 @@ struct PkMerit {
   size_t partial_cap = 0;           // ... in doubles
   double* d_scratch = nullptr;      // the host forms' [x | d | X | f | grad | g | J | out] for one chunk of entries: likewise
   size_t scratch_cap = 0;
+};
+
+// ---- CG on the condensed KKT matrix / the normal equations (pk_cg.cpp: pk_cg_begin_dev, pk_solve_condensed ...; free_cg, cg_forget)
+// Allocated on first use; every array grows when needed and never shrinks short of pk_set_problem.
+struct PkCg {
+  double* d_work = nullptr;         // [r | z | p | q | t], max(n, m) doubles each
+  size_t work_cap = 0;
+  double* d_partial = nullptr;      // the pieces' partial sums, 3 planes of n_pieces doubles
+  size_t partial_cap = 0;
+  double* d_rec = nullptr;          // the record of 8 doubles
+  size_t rec_cap = 0;
+  double* d_scratch = nullptr;      // the host forms' [b | x0 | x | d | s | minv | v], max(n, m) doubles each
+  size_t scratch_cap = 0;
+  // the solve in progress (pk_cg_begin_dev): the caller's arrays; forgotten by pk_set_csr_operator and pk_set_csr_map
+  bool active = false;
+  int form = 0;
+  const double *jvals = nullptr, *hvals = nullptr, *d = nullptr, *s = nullptr, *minv = nullptr;
+  double* x = nullptr;
+  hipStream_t stream = nullptr;     // where the last begin / advance was enqueued: pk_cg_record copies behind it
 };
 
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
@@ -312,6 +333,7 @@ struct pk_ctx : pk_error_state {
                      // + [3]: compact Jacobian values -> the CSR entries of J (the few repeated positions summed)
   PkOps ops;
   PkMerit merit;
+  PkCg cg;
   PkMeshError mesh_error;
   PkShim shim;
 };
@@ -402,6 +424,10 @@ int op_linearized(pk_ctx* c, int op, const double*& vals, const char* who);
 
 // ---- pk_merit.cpp
 void free_merit(pk_ctx* c);          // bounds, partial rows and scratch (with the problem)
+
+// ---- pk_cg.cpp
+void free_cg(pk_ctx* c);             // work vectors, partial sums, record and scratch (with the problem)
+void cg_forget(pk_ctx* c);           // a solve in progress is forgotten: the operators or a map are about to change
 
 // ---- the host-buffer form of an entry point: upload x (and lambda), the device-pointer entry point, download, synchronize
 inline int host_ready(pk_ctx* c, bool buffers) {

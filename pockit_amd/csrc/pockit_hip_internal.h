@@ -1,5 +1,5 @@
 /* pockit_hip_internal.h -- the entry points of libpockit_hip.so that are NOT part of its stable surface
- * (include/pockit_hip.h): 54 functions in four sections.  All of them are exported like the stable ones and follow the same
+ * (include/pockit_hip.h): 55 functions in four sections.  All of them are exported like the stable ones and follow the same
  * conventions (0 or an error code, pk_last_error); they serve this project's own binding (pockit_amd/runtime.py), its sharding
  * transport, its tools and tests, and change with them.  No function crossed the line in either direction when the header was
  * split: the stable header holds exactly the list of a foreign binding's needs.
@@ -172,7 +172,7 @@ int pk_copy_runs_dev(pk_ctx* ctx, const int64_t* d_table, int n_chunks, const do
  * poll such words instead of waiting for the other processes to notice that their GPU has finished) */
 int pk_store_word_dev(pk_ctx* ctx, void* d_dst, int64_t value, void* stream);
 
-/* ================================================================================================ Tuning and diagnostics (11) */
+/* ================================================================================================ Tuning and diagnostics (12) */
 /* `count` back-to-back cycles on the same buffers, enqueued by the library (a solver written against the C ABI launches from
  * compiled code; bench.py's timed batches go through this so that no interpreter loop paces the stream).  xchg = 1: every
  * cycle is followed by pk_exchange_sums_dev(d_x, d_xgrad, d_f) -- the two-launch form of a sharded cycle.  No reference
@@ -208,6 +208,16 @@ int pk_batch_launches(pk_ctx* ctx, int64_t* launches);
 int pk_merit_reduce_dev(pk_ctx* ctx, int B, int64_t n_g, const double* d_g, int64_t ldg, const double* d_clb, const double* d_cub,
                         int64_t n_x, const double* d_X, int64_t ldx, const double* d_vlb, const double* d_vub, const double* d_grad,
                         int64_t ldgrad, const double* d_d /* or NULL */, const double* d_f, double* d_out, void* stream);
+/* ONE vector step of the CG of pk_cg.cpp on an EXPLICIT length with caller-owned device vectors and record (the public forms call
+ * it with the context's vectors): so that tests can drive lengths a small model does not have.  The partial sums are the
+ * context's.  step: 0 init -- d_b, d_x0 or NULL (then d_q holds K x0 on entry), d_minv or NULL, d_s or NULL; writes x, r, z, p,
+ * q = s o p and the whole record from b.b, r.z, r.r and tol; 1 curvature -- pq = p.q and scalar step A; 2 update -- x, r, z,
+ * r.z, r.r and scalar step B, d_minv or NULL; 3 direction -- p = z + beta p while the status is 0, q = s o p always; 4 scale --
+ * q = s o q in place; 5 Jacobi -- q = 1 / |b + s| or 1.0, d_s or NULL.  Pointers a step does not use may be NULL.  Errors 110,
+ * 134 for step, len or tol, 136. */
+int pk_cg_step_dev(pk_ctx* ctx, int step, int64_t len, const double* d_b, const double* d_x0, const double* d_minv,
+                   const double* d_s, double* d_x, double* d_r, double* d_z, double* d_p, double* d_q, double* d_rec, double tol,
+                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -937,6 +937,44 @@ class Evaluator:
             raise ValueError('only "H" is square: J and JT have no diagonal')
         self.ctx.check(self.ctx.lib.pk_operator_diagonal_dev(self.ctx.handle, self._operator_diagonal(), d_vals, d_add, d_y, stream))
 
+    # ------------------------------------------------------------------ the condensed KKT matrix / the normal equations (csrc/pk_cg.cpp)
+    FORMS = {"primal": 0, "dual": 1}
+
+    def _condensed(self, form, with_h):
+        """Number of ``form`` for the C ABI, with the operators (and the map of H) it needs uploaded."""
+        if form not in self.FORMS:
+            raise ValueError('form must be "primal" or "dual"')
+        if self.src.sharded:
+            raise NotImplementedError("the condensed operator and its CG solve are not offered for a sharded evaluator")
+        if with_h and form == "dual":
+            raise ValueError("the dual form has no Hessian term")
+        for op in ("J", "JT") + (("H",) if with_h else ()):
+            self._operator(op)
+        return self.FORMS[form]
+
+    def condensed_apply_dev(self, form, d_jvals, d_v, d_y, d_hvals=None, d_d=None, d_s=None, stream=None):
+        """``y = K v`` on device pointers: ``form`` "primal" (``[H v] + J^T (d o (J v)) + s o v``, size n) or "dual"
+        (``J (d o (J^T v)) + s o v``, size m); ``d_hvals``, ``d_d`` and ``d_s`` may be None.  Enqueued, not waited for."""
+        k = self._condensed(form, d_hvals is not None)
+        self.ctx.check(self.ctx.lib.pk_condensed_apply_dev(self.ctx.handle, k, d_jvals, d_hvals, d_d, d_s, d_v, d_y, stream))
+
+    def cg_begin_dev(self, form, d_jvals, d_b, d_x, tol, d_hvals=None, d_d=None, d_s=None, d_minv=None, d_x0=None, stream=None):
+        """Begin a preconditioned CG solve of ``K x = b`` on device pointers (``pk_cg_begin_dev``): the arrays stay the
+        caller's and must stay valid until the solve ends.  Enqueued, not waited for."""
+        k = self._condensed(form, d_hvals is not None)
+        self.ctx.check(self.ctx.lib.pk_cg_begin_dev(self.ctx.handle, k, d_jvals, d_hvals, d_d, d_s, d_minv, d_b, d_x0, d_x, float(tol),
+                                                    stream))
+
+    def cg_advance_dev(self, iters, stream=None):
+        """Enqueue ``iters`` iterations of the solve in progress, without a synchronisation."""
+        self.ctx.check(self.ctx.lib.pk_cg_advance_dev(self.ctx.handle, int(iters), stream))
+
+    def cg_record(self):
+        """The record of the solve in progress (8 doubles: status, iterations, rr, thr, rz, pq, alpha, beta), waited for."""
+        rec = np.empty(8)
+        self.ctx.check(self.ctx.lib.pk_cg_record(self.ctx.handle, runtime.as_dp(rec)))
+        return rec
+
     def linearize(self, x, lagrange=None, obj_factor=1.0):
         """Evaluate J at ``x`` -- and the Hessian of the Lagrangian with ``(lagrange, obj_factor)`` unless ``lagrange`` is
         None -- into the context's CSR value arrays and leave them on the device: the ``Linearization`` returned multiplies
@@ -1300,6 +1338,39 @@ class Evaluator:
         return out
 
 
+class CgInfo:
+    """What a CG solve on the device reports (read-only): ``status`` by name, ``iterations``, ``rel_residual`` (of the
+    recurrence: ``sqrt(rr / bb)``), ``curvature`` (the last ``p^T K p``), ``alpha``, ``beta`` and the raw ``record``."""
+    STATUS = {0: "running", 1: "converged", 2: "non_positive_curvature", 3: "non_finite", 4: "maxiter"}
+    __slots__ = ("_rec", "_tol")
+
+    def __init__(self, rec, tol):
+        rec = np.array(rec, dtype=np.float64)
+        rec.setflags(write=False)
+        object.__setattr__(self, "_rec", rec)
+        object.__setattr__(self, "_tol", float(tol))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("CgInfo is read-only")
+
+    record = property(lambda self: self._rec)
+    status = property(lambda self: self.STATUS[int(self._rec[0])])
+    iterations = property(lambda self: int(self._rec[1]))
+    curvature = property(lambda self: float(self._rec[5]))
+    alpha = property(lambda self: float(self._rec[6]))
+    beta = property(lambda self: float(self._rec[7]))
+
+    @property
+    def rel_residual(self):
+        rr, thr = float(self._rec[2]), float(self._rec[3])      # thr = tol^2 b.b
+        if thr > 0.0:
+            return float(np.sqrt(rr / thr)) * self._tol
+        return 0.0 if rr == 0.0 else float("nan")      # (b = 0, or tol = 0: the record does not hold b.b itself)
+
+    def __repr__(self):
+        return f"CgInfo(status={self.status!r}, iterations={self.iterations}, curvature={self.curvature:.3e})"
+
+
 class Linearization:
     """J (and H) of one iterate, resident on the device (``Evaluator.linearize``): products with host vectors."""
 
@@ -1411,6 +1482,90 @@ class Linearization:
         """The diagonal of ``J^T diag(d) J`` (length n); ``with_h``: of ``H + J^T diag(d) J``, the condensed KKT matrix -- the
         diagonal of H is formed on the device and the sums are added to it there, one round trip."""
         return self._reduce("JT", "sq_sum", d, with_h=with_h)
+
+    # ---- the condensed KKT matrix and the normal equations: products and the CG solve on the device (csrc/pk_cg.cpp)
+    def _condensed_args(self, d, shift, form, with_h):
+        if form not in Evaluator.FORMS:
+            raise ValueError('form must be "primal" or "dual"')
+        if with_h is None:
+            with_h = self.has_hessian and form == "primal"
+        ev = self._check_live(bool(with_h))
+        size, other = (self.n, self.m) if form == "primal" else (self.m, self.n)
+        k = ev._condensed(form, bool(with_h))
+        if d is not None:
+            d = np.ascontiguousarray(d, dtype=np.float64)
+            if d.shape != (other,):
+                raise ValueError(f"d must have shape ({other},)")
+        if shift is not None:
+            shift = np.ascontiguousarray(np.broadcast_to(np.asarray(shift, dtype=np.float64), (size,)))
+        return ev, k, bool(with_h), size, d, shift
+
+    @staticmethod
+    def _opt(a):
+        return None if a is None else runtime.as_dp(a)
+
+    def kv(self, v, d=None, shift=None, form="primal", with_h=None):
+        """``K v``: ``form`` "primal" gives ``[H v] + J^T (d o (J v)) + shift o v`` (size n, ``d`` of m values), "dual"
+        ``J (d o (J^T v)) + shift o v`` (size m, ``d`` of n values).  ``d`` None: the identity; ``shift`` a scalar, a vector or
+        None; ``with_h`` None: H where the linearization has one.  One round trip."""
+        ev, k, with_h, size, d, shift = self._condensed_args(d, shift, form, with_h)
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (size,):
+            raise ValueError(f"the vector must have shape ({size},)")
+        y = np.empty(size)
+        ev.ctx.check(ev.ctx.lib.pk_condensed_apply(ev.ctx.handle, k, int(with_h), self._opt(d), self._opt(shift), runtime.as_dp(v),
+                                                   runtime.as_dp(y)))
+        return y
+
+    def condensed_operator(self, d=None, shift=None, form="primal", with_h=None):
+        """``kv`` with these arguments as a symmetric ``scipy.sparse.linalg.LinearOperator``."""
+        from scipy.sparse.linalg import LinearOperator
+
+        size = self.n if form == "primal" else self.m
+        mv = lambda v: self.kv(np.asarray(v).reshape(-1), d, shift, form, with_h)  # noqa: E731
+        return LinearOperator((size, size), matvec=mv, rmatvec=mv, dtype=np.float64)
+
+    def jacobi(self, d=None, shift=None, form="primal", with_h=None):
+        """The Jacobi preconditioner of ``K`` as ``solve_condensed(precond="jacobi")`` builds it on the device, bit for bit:
+        ``1 / |diag K|``, 1.0 where that is zero or not finite."""
+        _, _, with_h, _, d, shift = self._condensed_args(d, shift, form, with_h)
+        g = self.jtdj_diag(d, with_h=with_h) if form == "primal" else self.jdjt_diag(d)
+        a = np.abs(g if shift is None else g + shift)
+        good = (a > 0) & np.isfinite(a)
+        return np.where(good, 1.0 / np.where(good, a, 1.0), 1.0)
+
+    def solve_condensed(self, b, d=None, shift=None, *, form="primal", with_h=None, precond="jacobi", x0=None, tol=1e-8, maxiter=None,
+                        check_every=8):
+        """Solve ``K x = b`` (``kv``'s matrix) by preconditioned CG on the device: one call uploads ``b`` and downloads ``x``;
+        the iterations are launches with no synchronisation inside a chunk of ``check_every``.  ``precond``: "jacobi" (built on
+        the device), None, or an array ``minv`` applied as ``z = minv o r``.  Convergence is ``|r| <= tol |b|`` in the
+        recurrence.  Returns ``(x, info)``, ``info`` a ``CgInfo``."""
+        ev, k, with_h, size, d, shift = self._condensed_args(d, shift, form, with_h)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (size,):
+            raise ValueError(f"b must have shape ({size},)")
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (size,):
+                raise ValueError(f"x0 must have shape ({size},)")
+        minv = None
+        if precond is None:
+            mode = 0
+        elif isinstance(precond, str):
+            if precond != "jacobi":
+                raise ValueError('precond must be "jacobi", None or an array')
+            mode = 1
+            if with_h:
+                ev._operator_diagonal()
+        else:
+            mode, minv = 2, np.ascontiguousarray(precond, dtype=np.float64)
+            if minv.shape != (size,):
+                raise ValueError(f"the preconditioner must have shape ({size},)")
+        x, rec = np.empty(size), np.empty(8)
+        ev.ctx.check(ev.ctx.lib.pk_solve_condensed(ev.ctx.handle, k, int(with_h), self._opt(d), self._opt(shift), mode, self._opt(minv),
+                                                   runtime.as_dp(b), self._opt(x0), float(tol), int(size if maxiter is None else maxiter),
+                                                   int(check_every), runtime.as_dp(x), runtime.as_dp(rec)))
+        return x, CgInfo(rec, tol)
 
     def jacobian_operator(self):
         from scipy.sparse.linalg import LinearOperator

@@ -125,6 +125,12 @@ PROTOTYPES = {
     "pk_merit_batch_dev": (C.c_int, [vp, C.c_int, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]),
     "pk_merit_scan": (C.c_int, [vp, C.c_int64, dp, dp, dp, dp]),
     "pk_merit_batch": (C.c_int, [vp, C.c_int64, dp, C.c_int64, dp, dp]),
+    "pk_condensed_apply_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "pk_condensed_apply": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, dp, dp]),
+    "pk_cg_begin_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp]),
+    "pk_cg_advance_dev": (C.c_int, [vp, C.c_int, vp]),
+    "pk_cg_record": (C.c_int, [vp, dp]),
+    "pk_solve_condensed": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_int, dp, dp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -187,6 +193,7 @@ PROTOTYPES = {
     "pk_kernel_name": (C.c_char_p, [C.c_int]),
     "pk_merit_reduce_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64,
                                       vp, vp, vp, vp]),
+    "pk_cg_step_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp]),
 }
 EXPORTS = list(PROTOTYPES)
 
