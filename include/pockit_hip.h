@@ -1,8 +1,8 @@
 /* pockit_hip.h -- C ABI of the MI355X NLP-callback evaluator (libpockit_hip.so).
  *
- * STABLE SURFACE.  The 60 entry points declared here are the contract of the library: what a second host binding for
+ * STABLE SURFACE.  The 66 entry points declared here are the contract of the library: what a second host binding for
  * pockit's evaluator path needs -- life cycle, evaluation on host buffers and on device pointers, the compact layouts, the CSR
- * hand-off with its operators, reductions and the CG solve on them, batches with their merit terms, and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
+ * hand-off with its operators, reductions, the CG solve and the MINRES solve on them, batches with their merit terms, and mesh error estimation.  Everything else libpockit_hip.so exports (the plumbing of this project's own Python
  * shim, the sharding transport, the helper threads, tuning switches and diagnostics) is declared in
  * pockit_amd/csrc/pockit_hip_internal.h and may change with the project.
  *
@@ -381,6 +381,46 @@ int pk_cg_record(pk_ctx* ctx, double* rec /* 8 */);
 int pk_solve_condensed(pk_ctx* ctx, int form, int with_h, const double* d, const double* s, int precond,
                        const double* minv /* precond 2 */, const double* b, const double* x0 /* or NULL */, double tol, int maxiter,
                        int check_every, double* x, double* rec /* 8 */);
+
+/* THE AUGMENTED KKT SYSTEM, applied and solved by preconditioned MINRES where the linearization lies (kernels pk_mr_init,
+ * pk_mr_dot, pk_mr_update, pk_mr_scalar, pk_mr_elem of the library; pk_minres.cpp).  Symmetric and
+ * INDEFINITE, of size N = n + m, vectors [primal (n) | dual (m)] contiguous:
+ *   K = [ H + diag(s1)    J^T     ]     s1: n values or NULL (no term); s2: m values or NULL (no term: equality constraints);
+ *       [     J       -diag(s2)   ]     d_hvals NULL: no H
+ * One application runs in the fixed order q = (s1 o v1 | -(s2 o v2)) (or 0.0), q1 = H v1 + q1, q1 = J^T v2 + q1,
+ * q2 = J v1 + q2, the products pk_apply_operator_dev's with their association; no product is fused with a sum.
+ * pk_kkt_apply_dev enqueues one application y = K v; pk_kkt_apply does it on the values of pk_linearize, one round trip.
+ * The solve keeps a record of 16 doubles on the device: 0 status (0 running, 1 converged, 2 preconditioner not positive --
+ * r.Mr < 0 --, 3 non-finite scalar or gamma == 0), 1 completed iterations, 2 phibar (the recurrence's |b - K x| in the
+ * M-norm), 3 the threshold tol sqrt(b.(minv o b)), 4 beta, 5 oldb, 6 alfa, 7 dbar, 8 epsln, 9 cs, 10 sn, 11 phi, 12 oldeps,
+ * 13 delta, 14 gamma (Paige and Saunders' names), 15 internal (0 in every host copy).  pk_minres_begin_dev takes caller-owned
+ * device arrays that stay valid and unchanged until the solve ends -- d_s1, d_s2, d_minv (a diagonal POSITIVE preconditioner
+ * y = minv o r of N values, NULL: none) -- and d_x0 may be NULL; x (N values) is written to d_x; convergence is
+ * phibar <= tol sqrt(b.(minv o b)).  pk_minres_advance_dev enqueues iters iterations with no synchronisation; once the status is
+ * not 0 an iteration leaves x and the record untouched, so x, iterations and status do not depend on how many were enqueued
+ * beyond the stop.  pk_minres_record copies the record and synchronises.  One solve per context at a time; pk_set_csr_operator,
+ * pk_set_csr_map and pk_set_problem forget it.  The sums are associated in a fixed way: no atomics, the same bits every run.
+ * pk_solve_kkt is the host form on pk_linearize's values: uploads, the preconditioner -- precond 0 none, 1 diagonal, built on
+ * the device: minv1 = 1 / |diag H + s1|, minv2_i = 1 / |sum_j J_ij^2 minv1_j + s2_i|, 1.0 where the denominator is zero or not
+ * finite, 2 the caller's minv of N values -- begin, chunks of min(check_every, remaining) iterations each followed by a read of
+ * the record until the status is not 0 or maxiter iterations are done, then x (N values) comes down; exhaustion is status 4 in
+ * the host copy only, and a result: the call returns 0.
+ * Errors: 110 a null device pointer; 117 an operator is not set; 118 no (matching) linearization; 119 a sharded context;
+ * 132 precond 1 with H before pk_set_operator_diagonal; 134 tol negative or not finite, iters, maxiter or check_every below 1,
+ * precond out of range; 135 advance or record without a begin; 136 no device memory; 60 a null host buffer.  Nothing is
+ * enqueued after a refusal. */
+int pk_kkt_apply_dev(pk_ctx* ctx, const double* d_jvals, const double* d_hvals /* or NULL */, const double* d_s1 /* or NULL */,
+                     const double* d_s2 /* or NULL */, const double* d_v, double* d_y, void* stream);
+int pk_kkt_apply(pk_ctx* ctx, int with_h, const double* s1 /* or NULL */, const double* s2 /* or NULL */, const double* v,
+                 double* y);
+int pk_minres_begin_dev(pk_ctx* ctx, const double* d_jvals, const double* d_hvals /* or NULL */, const double* d_s1,
+                        const double* d_s2, const double* d_minv /* or NULL */, const double* d_b, const double* d_x0 /* or NULL */,
+                        double* d_x, double tol, void* stream);
+int pk_minres_advance_dev(pk_ctx* ctx, int iters, void* stream);
+int pk_minres_record(pk_ctx* ctx, double* rec /* 16 */);
+int pk_solve_kkt(pk_ctx* ctx, int with_h, const double* s1, const double* s2, int precond, const double* minv /* precond 2 */,
+                 const double* b, const double* x0 /* or NULL */, double tol, int maxiter, int check_every, double* x,
+                 double* rec /* 16 */);
 
 #ifdef __cplusplus
 }

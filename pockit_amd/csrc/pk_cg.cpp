@@ -307,8 +307,7 @@ void free_cg(pk_ctx* c) {
   c->cg = PkCg{};
 }
 
-namespace {
-
+// (shared with pk_minres.cpp: declared in pk_runtime.h)
 // an array of the context that grows when needed and never shrinks: the new one first, so error 136 enqueues nothing and
 // leaves what was there; work enqueued earlier may still use the old one, so the device is waited for
 int cg_reserve(pk_ctx* c, double*& p, size_t& cap, size_t want, const char* who, const char* what) {
@@ -327,6 +326,13 @@ int cg_reserve(pk_ctx* c, double*& p, size_t& cap, size_t want, const char* who,
   cap = want;
   return 0;
 }
+
+int cg_up(pk_ctx* c, double* dst, const double* src, size_t count) {
+  if (src && count) PK_HIP(c, hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+namespace {
 
 size_t cg_len(const pk_ctx* c) { return (size_t)std::max(std::max(c->n, c->m), 1); }
 
@@ -438,11 +444,6 @@ int cg_scratch(pk_ctx* c, CgScratch& s, const char* who) {
   if (const int rc = cg_reserve(c, c->cg.d_scratch, c->cg.scratch_cap, 7 * L, who, "host-form scratch")) return rc;
   double* w = c->cg.d_scratch;
   s = {w, w + L, w + 2 * L, w + 3 * L, w + 4 * L, w + 5 * L, w + 6 * L};
-  return 0;
-}
-
-int cg_up(pk_ctx* c, double* dst, const double* src, size_t count) {
-  if (src && count) PK_HIP(c, hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
   return 0;
 }
 

@@ -1,5 +1,5 @@
 // pk_libkernel.h -- private to the units whose kernels are compiled into the library itself, not into a model's code object
-// (pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp): what such a unit needs around its own arithmetic, stated once.
+// (pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp, pk_minres.cpp): what such a unit needs around its own arithmetic, stated once.
 //
 // A unit writes the work of one thread as PK_LIB_FN functions.  Under __HIPCC__ its kernels call them between barriers; without
 // it (the CPU-only builds of tests/fake_hip) a host function walks the same work items with the same grid stride, thread by

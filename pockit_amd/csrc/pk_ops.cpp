@@ -301,6 +301,7 @@ void free_operators(pk_ctx* c) {
   c->ops.scratch_k = 0;
   c->ops.lin_J = c->ops.lin_H = nullptr;
   cg_forget(c);      // (a solve in progress holds pointers into what the operators were built from)
+  minres_forget(c);
 }
 
 void drop_linearization(pk_ctx* c) { c->ops.lin_J = c->ops.lin_H = nullptr; }
@@ -358,6 +359,7 @@ int pk_set_csr_operator(pk_ctx* c, int op, const int32_t* indptr, const int32_t*
   PkOperator& o = c->ops.op[op];
   free_operator(o);
   cg_forget(c);
+  minres_forget(c);
   if ((rc = upload(c, (void**)&o.d_indptr, indptr, sizeof(int32_t) * ((size_t)n_rows + 1)))) return rc;
   if ((rc = upload(c, (void**)&o.d_indices, indices, sizeof(int32_t) * (size_t)nnz))) return rc;
   if (src && (rc = upload(c, (void**)&o.d_src, src, sizeof(int32_t) * (size_t)nnz))) return rc;

@@ -14,9 +14,11 @@
 //                   own kernels), the bounds they are measured against, the scratch of the host forms
 //   pk_cg.cpp       the condensed KKT matrix and the normal equations applied and solved by preconditioned CG on the device
 //                   (pk_cg_init, pk_cg_dot, pk_cg_update, pk_cg_scalar, pk_cg_elem: the library's own kernels), its work vectors
+//   pk_minres.cpp   the augmented (indefinite) KKT system applied and solved by preconditioned MINRES on the device
+//                   (pk_mr_init, pk_mr_dot, pk_mr_update, pk_mr_scalar, pk_mr_elem: the library's own kernels), its work vectors
 //   pk_error.cpp    fail(): where an error message is kept
 //
-// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp and pk_cg.cpp share beyond it: the scaffolding of kernels that
+// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp and pk_minres.cpp share beyond it: the scaffolding of kernels that
 // are compiled into the library (function macro, tree driver, grid rule, host walk, launch).
 //
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
@@ -183,6 +185,24 @@ struct PkCg {
   hipStream_t stream = nullptr;     // where the last begin / advance was enqueued: pk_cg_record copies behind it
 };
 
+// ---- MINRES on the augmented KKT system (pk_minres.cpp: pk_minres_begin_dev, pk_solve_kkt ...; free_minres, minres_forget)
+// Allocated on first use; every array grows when needed and never shrinks short of pk_set_problem.
+struct PkMinres {
+  double* d_work = nullptr;         // [r1 | r2 | y | v | w | w2 | q], n + m doubles each
+  size_t work_cap = 0;
+  double* d_partial = nullptr;      // the pieces' partial sums, 2 planes of n_pieces doubles
+  size_t partial_cap = 0;
+  double* d_rec = nullptr;          // the record of 16 doubles
+  size_t rec_cap = 0;
+  double* d_scratch = nullptr;      // the host forms' [b | x0 | x | s1 s2 | minv | v], n + m doubles each
+  size_t scratch_cap = 0;
+  // the solve in progress (pk_minres_begin_dev): the caller's arrays; forgotten by pk_set_csr_operator and pk_set_csr_map
+  bool active = false;
+  const double *jvals = nullptr, *hvals = nullptr, *s1 = nullptr, *s2 = nullptr, *minv = nullptr;
+  double* x = nullptr;
+  hipStream_t stream = nullptr;     // where the last begin / advance was enqueued: pk_minres_record copies behind it
+};
+
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
 struct PkMeshError {
   void* d_iv = nullptr;
@@ -334,6 +354,7 @@ struct pk_ctx : pk_error_state {
   PkOps ops;
   PkMerit merit;
   PkCg cg;
+  PkMinres minres;
   PkMeshError mesh_error;
   PkShim shim;
 };
@@ -428,6 +449,14 @@ void free_merit(pk_ctx* c);          // bounds, partial rows and scratch (with t
 // ---- pk_cg.cpp
 void free_cg(pk_ctx* c);             // work vectors, partial sums, record and scratch (with the problem)
 void cg_forget(pk_ctx* c);           // a solve in progress is forgotten: the operators or a map are about to change
+// An array of the context that grows when needed and never shrinks: the new one first, so error 136 enqueues nothing and leaves
+// what was there.  And the upload of an optional host array on the context's stream.  (Shared with pk_minres.cpp.)
+int cg_reserve(pk_ctx* c, double*& p, size_t& cap, size_t want, const char* who, const char* what);
+int cg_up(pk_ctx* c, double* dst, const double* src, size_t count);
+
+// ---- pk_minres.cpp
+void free_minres(pk_ctx* c);         // work vectors, partial sums, record and scratch (with the problem)
+void minres_forget(pk_ctx* c);       // a solve in progress is forgotten: the operators or a map are about to change
 
 // ---- the host-buffer form of an entry point: upload x (and lambda), the device-pointer entry point, download, synchronize
 inline int host_ready(pk_ctx* c, bool buffers) {

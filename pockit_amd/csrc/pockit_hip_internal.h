@@ -218,6 +218,18 @@ int pk_merit_reduce_dev(pk_ctx* ctx, int B, int64_t n_g, const double* d_g, int6
 int pk_cg_step_dev(pk_ctx* ctx, int step, int64_t len, const double* d_b, const double* d_x0, const double* d_minv,
                    const double* d_s, double* d_x, double* d_r, double* d_z, double* d_p, double* d_q, double* d_rec, double tol,
                    void* stream);
+/* ONE vector step of the MINRES of pk_minres.cpp on an EXPLICIT length and an EXPLICIT split index (the first index of the second
+ * diagonal block, 0 <= split <= len) with caller-owned device vectors and record of 16 doubles (the public forms call it with
+ * the context's vectors, len = n + m, split = n).  The partial sums are the context's.  step: 0 begin -- d_b, d_x0 or NULL (then
+ * d_q holds K x0 on entry), d_minv or NULL; writes x, r1, r2, y, w = w2 = 0 and the whole record from b.(minv o b), r1.y and
+ * tol; 1 Lanczos vector -- v = (1 / beta) y while the status is 0, q = the diagonal blocks' terms of v always (d_s1, d_s2 or
+ * NULL); 2 alfa -- v.q and scalar step A; 3 update -- r1, r2, y, the sum of t y and scalar step B, d_minv or NULL; 4 solution
+ * update -- w2, w, x when the record's slot 15 is 1; 5 diagonal blocks -- q = the terms of b (d_s1, d_s2 or NULL); 6 reciprocal
+ * -- q = 1 / |b + s1| or 1.0 (d_b NULL: 0.0, d_s1 or NULL).  Pointers a step does not use may be NULL.  Errors 110, 134 for
+ * step, len, split or tol, 136. */
+int pk_minres_step_dev(pk_ctx* ctx, int step, int64_t len, int64_t split, const double* d_b, const double* d_x0, const double* d_minv,
+                       const double* d_s1, const double* d_s2, double* d_x, double* d_r1, double* d_r2, double* d_y, double* d_v,
+                       double* d_w, double* d_w2, double* d_q, double* d_rec, double tol, void* stream);
 
 #ifdef __cplusplus
 }

@@ -975,6 +975,38 @@ class Evaluator:
         self.ctx.check(self.ctx.lib.pk_cg_record(self.ctx.handle, runtime.as_dp(rec)))
         return rec
 
+    # ------------------------------------------------------------------ the augmented KKT system (csrc/pk_minres.cpp)
+    def _kkt(self, with_h):
+        """The operators (and the map of H) the augmented system needs, uploaded."""
+        if self.src.sharded:
+            raise NotImplementedError("the augmented KKT operator and its MINRES solve are not offered for a sharded evaluator")
+        for op in ("J", "JT") + (("H",) if with_h else ()):
+            self._operator(op)
+
+    def kkt_apply_dev(self, d_jvals, d_v, d_y, d_hvals=None, d_s1=None, d_s2=None, stream=None):
+        """``y = K v`` on device pointers, ``K = [[H + diag(s1), J^T], [J, -diag(s2)]]`` of size n + m, vectors
+        ``[primal | dual]``; ``d_hvals``, ``d_s1`` and ``d_s2`` may be None.  Enqueued, not waited for."""
+        self._kkt(d_hvals is not None)
+        self.ctx.check(self.ctx.lib.pk_kkt_apply_dev(self.ctx.handle, d_jvals, d_hvals, d_s1, d_s2, d_v, d_y, stream))
+
+    def minres_begin_dev(self, d_jvals, d_b, d_x, tol, d_hvals=None, d_s1=None, d_s2=None, d_minv=None, d_x0=None, stream=None):
+        """Begin a preconditioned MINRES solve of ``K x = b`` on device pointers (``pk_minres_begin_dev``): the arrays stay the
+        caller's and must stay valid until the solve ends.  Enqueued, not waited for."""
+        self._kkt(d_hvals is not None)
+        self.ctx.check(self.ctx.lib.pk_minres_begin_dev(self.ctx.handle, d_jvals, d_hvals, d_s1, d_s2, d_minv, d_b, d_x0, d_x,
+                                                        float(tol), stream))
+
+    def minres_advance_dev(self, iters, stream=None):
+        """Enqueue ``iters`` iterations of the MINRES solve in progress, without a synchronisation."""
+        self.ctx.check(self.ctx.lib.pk_minres_advance_dev(self.ctx.handle, int(iters), stream))
+
+    def minres_record(self):
+        """The record of the MINRES solve in progress (16 doubles: status, iterations, phibar, thr, beta, oldb, alfa, dbar,
+        epsln, cs, sn, phi, oldeps, delta, gamma, 0), waited for."""
+        rec = np.empty(16)
+        self.ctx.check(self.ctx.lib.pk_minres_record(self.ctx.handle, runtime.as_dp(rec)))
+        return rec
+
     def linearize(self, x, lagrange=None, obj_factor=1.0):
         """Evaluate J at ``x`` -- and the Hessian of the Lagrangian with ``(lagrange, obj_factor)`` unless ``lagrange`` is
         None -- into the context's CSR value arrays and leave them on the device: the ``Linearization`` returned multiplies
@@ -1371,6 +1403,39 @@ class CgInfo:
         return f"CgInfo(status={self.status!r}, iterations={self.iterations}, curvature={self.curvature:.3e})"
 
 
+class MinresInfo:
+    """What a MINRES solve on the device reports (read-only): ``status`` by name, ``iterations``, ``rel_residual`` (of the
+    recurrence, in the preconditioner's norm: ``phibar / sqrt(b.M b)``), ``primal`` and ``dual`` (views of the solution's two
+    blocks) and the raw ``record`` of 16 doubles."""
+    STATUS = {0: "running", 1: "converged", 2: "preconditioner_not_positive", 3: "non_finite", 4: "maxiter"}
+    __slots__ = ("_rec", "_tol", "_x", "_n")
+
+    def __init__(self, rec, tol, x, n):
+        rec = np.array(rec, dtype=np.float64)
+        rec.setflags(write=False)
+        for name, value in (("_rec", rec), ("_tol", float(tol)), ("_x", x), ("_n", int(n))):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("MinresInfo is read-only")
+
+    record = property(lambda self: self._rec)
+    status = property(lambda self: self.STATUS[int(self._rec[0])])
+    iterations = property(lambda self: int(self._rec[1]))
+    primal = property(lambda self: self._x[: self._n])
+    dual = property(lambda self: self._x[self._n:])
+
+    @property
+    def rel_residual(self):
+        phibar, thr = float(self._rec[2]), float(self._rec[3])      # thr = tol sqrt(b.M b)
+        if thr > 0.0:
+            return phibar / thr * self._tol
+        return 0.0 if phibar == 0.0 else float("nan")      # (b = 0, or tol = 0: the record does not hold b.M b itself)
+
+    def __repr__(self):
+        return f"MinresInfo(status={self.status!r}, iterations={self.iterations}, rel_residual={self.rel_residual:.3e})"
+
+
 class Linearization:
     """J (and H) of one iterate, resident on the device (``Evaluator.linearize``): products with host vectors."""
 
@@ -1566,6 +1631,92 @@ class Linearization:
                                                    runtime.as_dp(b), self._opt(x0), float(tol), int(size if maxiter is None else maxiter),
                                                    int(check_every), runtime.as_dp(x), runtime.as_dp(rec)))
         return x, CgInfo(rec, tol)
+
+    # ---- the augmented (indefinite) KKT system: products and the MINRES solve on the device (csrc/pk_minres.cpp)
+    def _kkt_args(self, s1, s2, with_h):
+        if with_h is None:
+            with_h = self.has_hessian
+        ev = self._check_live(bool(with_h))
+        ev._kkt(bool(with_h))
+        if s1 is not None:
+            s1 = np.ascontiguousarray(np.broadcast_to(np.asarray(s1, dtype=np.float64), (self.n,)))
+        if s2 is not None:
+            s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(s2, dtype=np.float64), (self.m,)))
+        return ev, bool(with_h), s1, s2
+
+    def kkt_v(self, v, s1=None, s2=None, with_h=None):
+        """``K v`` for ``K = [[H + diag(s1), J^T], [J, -diag(s2)]]`` and ``v = [primal (n) | dual (m)]``.  ``s1`` and ``s2``: a
+        scalar, a vector or None (no term; ``s2`` None: equality constraints); ``with_h`` None: H where the linearization has
+        one.  One round trip."""
+        ev, with_h, s1, s2 = self._kkt_args(s1, s2, with_h)
+        size = self.n + self.m
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (size,):
+            raise ValueError(f"the vector must have shape ({size},)")
+        y = np.empty(size)
+        ev.ctx.check(ev.ctx.lib.pk_kkt_apply(ev.ctx.handle, int(with_h), self._opt(s1), self._opt(s2), runtime.as_dp(v), runtime.as_dp(y)))
+        return y
+
+    def kkt_operator(self, s1=None, s2=None, with_h=None):
+        """``kkt_v`` with these arguments as a symmetric ``scipy.sparse.linalg.LinearOperator``."""
+        from scipy.sparse.linalg import LinearOperator
+
+        size = self.n + self.m
+        mv = lambda v: self.kkt_v(np.asarray(v).reshape(-1), s1, s2, with_h)  # noqa: E731
+        return LinearOperator((size, size), matvec=mv, rmatvec=mv, dtype=np.float64)
+
+    @staticmethod
+    def _recip(a):
+        a = np.abs(a)
+        good = (a > 0) & np.isfinite(a)
+        return np.where(good, 1.0 / np.where(good, a, 1.0), 1.0)
+
+    def kkt_precond(self, s1=None, s2=None, with_h=None):
+        """The diagonal preconditioner of ``K`` as ``solve_kkt(precond="diagonal")`` builds it on the device, bit for bit:
+        ``minv1 = 1 / |diag H + s1|``, ``minv2_i = 1 / |sum_j J_ij^2 minv1_j + s2_i|``, 1.0 where a denominator is zero or not
+        finite (length n + m, positive)."""
+        _, with_h, s1, s2 = self._kkt_args(s1, s2, with_h)
+        g1 = self.h_diag() if with_h else None
+        if g1 is None:
+            minv1 = np.ones(self.n) if s1 is None else self._recip(s1)
+        else:
+            minv1 = self._recip(g1 if s1 is None else g1 + s1)
+        g2 = self._reduce("J", "sq_sum", minv1)
+        return np.concatenate((minv1, self._recip(g2 if s2 is None else g2 + s2)))
+
+    def solve_kkt(self, b, s1=None, s2=None, *, with_h=None, precond="diagonal", x0=None, tol=1e-8, maxiter=None, check_every=8):
+        """Solve ``K x = b`` (``kkt_v``'s symmetric indefinite matrix) by preconditioned MINRES on the device: one call uploads
+        ``b`` and downloads ``x``; the iterations are launches with no synchronisation inside a chunk of ``check_every``.
+        ``precond``: "diagonal" (built on the device, ``kkt_precond``), None, or a positive array ``minv`` of n + m values
+        applied as ``y = minv o r``.  Convergence is ``|r|_M <= tol |b|_M`` in the recurrence.  Returns ``(x, info)``,
+        ``info`` a ``MinresInfo``."""
+        ev, with_h, s1, s2 = self._kkt_args(s1, s2, with_h)
+        size = self.n + self.m
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (size,):
+            raise ValueError(f"b must have shape ({size},)")
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (size,):
+                raise ValueError(f"x0 must have shape ({size},)")
+        minv = None
+        if precond is None:
+            mode = 0
+        elif isinstance(precond, str):
+            if precond != "diagonal":
+                raise ValueError('precond must be "diagonal", None or an array')
+            mode = 1
+            if with_h:
+                ev._operator_diagonal()
+        else:
+            mode, minv = 2, np.ascontiguousarray(precond, dtype=np.float64)
+            if minv.shape != (size,):
+                raise ValueError(f"the preconditioner must have shape ({size},)")
+        x, rec = np.empty(size), np.empty(16)
+        ev.ctx.check(ev.ctx.lib.pk_solve_kkt(ev.ctx.handle, int(with_h), self._opt(s1), self._opt(s2), mode, self._opt(minv),
+                                             runtime.as_dp(b), self._opt(x0), float(tol), int(2 * size if maxiter is None else maxiter),
+                                             int(check_every), runtime.as_dp(x), runtime.as_dp(rec)))
+        return x, MinresInfo(rec, tol, x, self.n)
 
     def jacobian_operator(self):
         from scipy.sparse.linalg import LinearOperator

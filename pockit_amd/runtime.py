@@ -131,6 +131,12 @@ PROTOTYPES = {
     "pk_cg_advance_dev": (C.c_int, [vp, C.c_int, vp]),
     "pk_cg_record": (C.c_int, [vp, dp]),
     "pk_solve_condensed": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_int, dp, dp]),
+    "pk_kkt_apply_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pk_kkt_apply": (C.c_int, [vp, C.c_int, dp, dp, dp, dp]),
+    "pk_minres_begin_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp]),
+    "pk_minres_advance_dev": (C.c_int, [vp, C.c_int, vp]),
+    "pk_minres_record": (C.c_int, [vp, dp]),
+    "pk_solve_kkt": (C.c_int, [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_int, dp, dp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -194,6 +200,8 @@ PROTOTYPES = {
     "pk_merit_reduce_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64,
                                       vp, vp, vp, vp]),
     "pk_cg_step_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp]),
+    "pk_minres_step_dev": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     C.c_double, vp]),
 }
 EXPORTS = list(PROTOTYPES)
 
