@@ -34,15 +34,12 @@
 // Once status != 0 further enqueued iterations leave x, r, z, p and the record untouched (q and t are scratch): x, iterations
 // and status do not depend on how many iterations were enqueued beyond the stop.
 //
-// Every product is rounded before its sum: nothing here contracts to a fused multiply-add.  The dots have the association of
-// pk_merit.cpp: index i belongs to piece i / 2048; thread t of the piece adds the terms at
-// piece * 2048 + t + 256 j, j = 0 ... 7, in ascending j to 0.0 (an index beyond the length adds nothing); the 256 thread values
-// meet in LDS and are reduced by the fixed tree of widths 128 ... 1 (slot t += slot t + w), one LDS plane per simultaneous dot
-// (three in begin: b.b, r.z, r.r; two in the update: r.z, r.r); partial[plane * n_pieces + piece].  The scalar step is one
-// workgroup: thread t adds the pieces t, t + 256, ... in ascending order to 0.0, the same tree follows, thread 0 does the
-// arithmetic above.  n_pieces = max(1, ceil(len / 2048)).  No atomics, no dependence on the grid, the same bits from run to run.
-// The update's work item is a piece (it updates and reduces in one pass); the purely elementwise kernels (direction, t = d o t,
-// the Jacobi reciprocal, q = s o v) take 256 elements per item; the grid rule is lib_grid.
+// Every product is rounded before its sum: nothing here contracts to a fused multiply-add.  The dots are the pieced dots of
+// pk_libkernel.h (pieces of 2048, 8 terms per thread, the fixed tree, the one-workgroup scalar step), one LDS plane per
+// simultaneous dot: three in begin (b.b, r.z, r.r), one in the curvature, two in the update (r.z, r.r).  The update's work item
+// is a piece (it updates and reduces in one pass); the purely elementwise kernels (direction, t = d o t, the Jacobi reciprocal,
+// q = s o v) take 256 elements per item; the grid rule is lib_grid.  The host side of a solve -- the context's arrays, the
+// checks, the skeletons of record / advance and of the host form's loop -- is pk_solve.cpp's.
 //
 // Jacobi: g = diag(K) from pk_operator_reduce_dev (sq_sum, w = d, add = diag H), then a = |g + s|,
 // minv = (a > 0 && finite(a)) ? 1 / a : 1.0                                                                          [pk_cg_elem]
@@ -57,7 +54,7 @@
 
 #include "pk_libkernel.h"      // (behind the pragma: what its templates are instantiated with is this unit's arithmetic)
 
-enum { PK_CG_PER_THREAD = 8, PK_CG_PIECE = PK_BLOCK * PK_CG_PER_THREAD, PK_CG_PLANES = 3, PK_CG_REC = 8 };
+enum { PK_CG_PLANES = 3, PK_CG_REC = 8 };
 enum { CG_STATUS = 0, CG_ITERS = 1, CG_RR = 2, CG_THR = 3, CG_RZ = 4, CG_PQ = 5, CG_ALPHA = 6, CG_BETA = 7 };
 enum { PK_CG_INIT = 0, PK_CG_CURVATURE = 1, PK_CG_UPDATE = 2, PK_CG_DIRECTION = 3, PK_CG_SCALE = 4, PK_CG_JACOBI = 5,
        PK_CG_DIAG = 6 };      // (PK_CG_DIAG: step 1 of an application, used inside the unit only)
@@ -71,14 +68,11 @@ struct PkCgArgs {
   int32_t kind, planes;                 // of the scalar step: PK_CG_INIT, PK_CG_CURVATURE, PK_CG_UPDATE, and the dots it adds
 };
 
-static int64_t cg_pieces(int64_t len) { return std::max<int64_t>(1, (len + PK_CG_PIECE - 1) / PK_CG_PIECE); }
-static int64_t cg_items(int64_t len) { return (len + PK_BLOCK - 1) / PK_BLOCK; }
-
 // ---------------------------------------------------------------- thread t of piece pc: its elements, its terms into the planes
 PK_LIB_FN void cg_init_thread(const PkCgArgs& a, int64_t pc, int t, double* s) {
   double bb = 0.0, rz = 0.0, rr = 0.0;
-  for (int j = 0; j < PK_CG_PER_THREAD; ++j) {
-    const int64_t i = pc * PK_CG_PIECE + t + (int64_t)PK_BLOCK * j;
+  for (int j = 0; j < PK_LIB_PER_THREAD; ++j) {
+    const int64_t i = pc * PK_LIB_PIECE + t + (int64_t)PK_BLOCK * j;
     if (i < a.len) {
       const double bi = a.b[i];
       const double ri = a.x0 ? bi - a.q[i] : bi;      // (with x0 the products left K x0 in q)
@@ -99,8 +93,8 @@ PK_LIB_FN void cg_init_thread(const PkCgArgs& a, int64_t pc, int t, double* s) {
 
 PK_LIB_FN void cg_dot_thread(const PkCgArgs& a, int64_t pc, int t, double* s) {
   double pq = 0.0;
-  for (int j = 0; j < PK_CG_PER_THREAD; ++j) {
-    const int64_t i = pc * PK_CG_PIECE + t + (int64_t)PK_BLOCK * j;
+  for (int j = 0; j < PK_LIB_PER_THREAD; ++j) {
+    const int64_t i = pc * PK_LIB_PIECE + t + (int64_t)PK_BLOCK * j;
     if (i < a.len) {
       const double term = a.p[i] * a.q[i];
       pq = pq + term;
@@ -111,8 +105,8 @@ PK_LIB_FN void cg_dot_thread(const PkCgArgs& a, int64_t pc, int t, double* s) {
 
 PK_LIB_FN void cg_update_thread(const PkCgArgs& a, int64_t pc, int t, double alpha, double* s) {
   double rz = 0.0, rr = 0.0;
-  for (int j = 0; j < PK_CG_PER_THREAD; ++j) {
-    const int64_t i = pc * PK_CG_PIECE + t + (int64_t)PK_BLOCK * j;
+  for (int j = 0; j < PK_LIB_PER_THREAD; ++j) {
+    const int64_t i = pc * PK_LIB_PIECE + t + (int64_t)PK_BLOCK * j;
     if (i < a.len) {
       const double ap = alpha * a.p[i], aq = alpha * a.q[i];
       const double xi = a.x[i] + ap, ri = a.r[i] - aq;
@@ -126,26 +120,6 @@ PK_LIB_FN void cg_update_thread(const PkCgArgs& a, int64_t pc, int t, double alp
     }
   }
   s[0 * PK_BLOCK + t] = rz; s[1 * PK_BLOCK + t] = rr;
-}
-
-// one step of the trees of `planes` dots, which share the barrier of the level: widths 128, 64 ... 1
-PK_LIB_FN void cg_tree_step(double* s, int w, int t, int planes) {
-  if (t >= w) return;
-  for (int q = 0; q < planes; ++q) s[q * PK_BLOCK + t] = s[q * PK_BLOCK + t] + s[q * PK_BLOCK + t + w];
-}
-
-// thread q < planes behind the trees
-PK_LIB_FN void cg_store_partial(const PkCgArgs& a, int64_t pc, int q, const double* s) {
-  a.partial[(int64_t)q * a.n_pieces + pc] = s[q * PK_BLOCK];
-}
-
-// thread t of the scalar step: per plane the pieces t, t + 256, ... in ascending order
-PK_LIB_FN void cg_scalar_thread(const PkCgArgs& a, int t, double* s) {
-  for (int q = 0; q < a.planes; ++q) {
-    double acc = 0.0;
-    for (int64_t pc = t; pc < a.n_pieces; pc += PK_BLOCK) acc = acc + a.partial[(int64_t)q * a.n_pieces + pc];
-    s[q * PK_BLOCK + t] = acc;
-  }
 }
 
 // thread 0 of the scalar step behind the trees: plane q ended in s[q * PK_BLOCK]
@@ -210,8 +184,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_cg_init(PkCgArgs a) {
   for (int64_t pc = (int64_t)blockIdx.x; pc < a.n_pieces; pc += (int64_t)gridDim.x) {
     cg_init_thread(a, pc, t, s);
     __syncthreads();
-    lib_tree(cg_tree_step, s, t, 3);
-    if (t < 3) cg_store_partial(a, pc, t, s);
+    lib_tree(lib_planes_step, s, t, 3);
+    if (t < 3) lib_store_partial(a, pc, t, s);
     __syncthreads();          // the next piece of this workgroup's stride overwrites the planes
   }
 }
@@ -222,8 +196,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_cg_dot(PkCgArgs a) {
   for (int64_t pc = (int64_t)blockIdx.x; pc < a.n_pieces; pc += (int64_t)gridDim.x) {
     cg_dot_thread(a, pc, t, s);
     __syncthreads();
-    lib_tree(cg_tree_step, s, t, 1);
-    if (t < 1) cg_store_partial(a, pc, t, s);
+    lib_tree(lib_planes_step, s, t, 1);
+    if (t < 1) lib_store_partial(a, pc, t, s);
     __syncthreads();
   }
 }
@@ -236,8 +210,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_cg_update(PkCgArgs a) {
   for (int64_t pc = (int64_t)blockIdx.x; pc < a.n_pieces; pc += (int64_t)gridDim.x) {
     cg_update_thread(a, pc, t, alpha, s);
     __syncthreads();
-    lib_tree(cg_tree_step, s, t, 2);
-    if (t < 2) cg_store_partial(a, pc, t, s);
+    lib_tree(lib_planes_step, s, t, 2);
+    if (t < 2) lib_store_partial(a, pc, t, s);
     __syncthreads();
   }
 }
@@ -245,9 +219,9 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_cg_update(PkCgArgs a) {
 __global__ void __launch_bounds__(PK_BLOCK) pk_cg_scalar(PkCgArgs a) {
   __shared__ double s[PK_CG_PLANES * PK_BLOCK];
   const int t = (int)threadIdx.x;
-  cg_scalar_thread(a, t, s);
+  lib_scalar_thread(a, t, s);
   __syncthreads();
-  lib_tree(cg_tree_step, s, t, a.planes);
+  lib_tree(lib_planes_step, s, t, a.planes);
   if (t == 0) cg_scalar_decide(a, s);
 }
 
@@ -259,113 +233,47 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_cg_elem(PkCgArgs a) {
 }
 #else
 // ---------------------------------------------------------------- host stand-in: the identical walk
-template <class Thread>
-static void cg_pieces_host(const PkCgArgs& a, unsigned grid, int planes, Thread thread) {
-  double s[PK_CG_PLANES * PK_BLOCK];
-  lib_walk_host(grid, a.n_pieces, [&](int64_t pc) {
-    for (int t = 0; t < PK_BLOCK; ++t) thread(pc, t, s);
-    lib_tree_host(cg_tree_step, s, planes);
-    for (int q = 0; q < planes; ++q) cg_store_partial(a, pc, q, s);
-  });
-}
-
 static void cg_init_host(const PkCgArgs& a, unsigned grid) {
-  cg_pieces_host(a, grid, 3, [&](int64_t pc, int t, double* s) { cg_init_thread(a, pc, t, s); });
+  lib_pieces_host<PK_CG_PLANES>(a, grid, 3, [&](int64_t pc, int t, double* s) { cg_init_thread(a, pc, t, s); });
 }
 static void cg_dot_host(const PkCgArgs& a, unsigned grid) {
-  cg_pieces_host(a, grid, 1, [&](int64_t pc, int t, double* s) { cg_dot_thread(a, pc, t, s); });
+  lib_pieces_host<PK_CG_PLANES>(a, grid, 1, [&](int64_t pc, int t, double* s) { cg_dot_thread(a, pc, t, s); });
 }
 static void cg_update_host(const PkCgArgs& a, unsigned grid) {
   if (a.rec[CG_STATUS] != 0.0) return;
   const double alpha = a.rec[CG_ALPHA];
-  cg_pieces_host(a, grid, 2, [&](int64_t pc, int t, double* s) { cg_update_thread(a, pc, t, alpha, s); });
+  lib_pieces_host<PK_CG_PLANES>(a, grid, 2, [&](int64_t pc, int t, double* s) { cg_update_thread(a, pc, t, alpha, s); });
 }
-static void cg_scalar_host(const PkCgArgs& a, unsigned) {
-  double s[PK_CG_PLANES * PK_BLOCK];
-  for (int t = 0; t < PK_BLOCK; ++t) cg_scalar_thread(a, t, s);
-  lib_tree_host(cg_tree_step, s, (int)a.planes);
-  cg_scalar_decide(a, s);
-}
+static void cg_scalar_host(const PkCgArgs& a, unsigned) { lib_scalar_host<PK_CG_PLANES>(a, cg_scalar_decide); }
 static void cg_elem_host(const PkCgArgs& a, unsigned grid) {
   const bool running = a.kind == PK_CG_DIRECTION && a.rec[CG_STATUS] == 0.0;
   const double beta = running ? a.rec[CG_BETA] : 0.0;
-  lib_walk_host(grid, cg_items(a.len), [&](int64_t item) {
-    for (int64_t i = item * PK_BLOCK; i < std::min<int64_t>(a.len, (item + 1) * PK_BLOCK); ++i) cg_element(a, i, running, beta);
-  });
+  lib_elements_host(grid, a.len, [&](int64_t i) { cg_element(a, i, running, beta); });
 }
 #endif
-
-void cg_forget(pk_ctx* c) {
-  PkCg& g = c->cg;
-  g.active = false;
-  g.jvals = g.hvals = g.d = g.s = g.minv = nullptr;
-  g.x = nullptr;
-}
-
-void free_cg(pk_ctx* c) {
-  release(c->cg.d_work); release(c->cg.d_partial); release(c->cg.d_rec); release(c->cg.d_scratch);
-  c->cg = PkCg{};
-}
-
-// (shared with pk_minres.cpp: declared in pk_runtime.h)
-// an array of the context that grows when needed and never shrinks: the new one first, so error 136 enqueues nothing and
-// leaves what was there; work enqueued earlier may still use the old one, so the device is waited for
-int cg_reserve(pk_ctx* c, double*& p, size_t& cap, size_t want, const char* who, const char* what) {
-  if (want <= cap) return 0;
-  PK_HIP(c, hipSetDevice(c->device));
-  double* q = nullptr;
-  if (hipMalloc((void**)&q, sizeof(double) * want) != hipSuccess || !q)
-    return fail(c, 136, "%s: no device memory for %zu doubles of %s", who, want, what);
-  const hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    release(q);
-    return fail(c, 100 + (int)e, "hipDeviceSynchronize failed: %s", hipGetErrorString(e));
-  }
-  release(p);
-  p = q;
-  cap = want;
-  return 0;
-}
-
-int cg_up(pk_ctx* c, double* dst, const double* src, size_t count) {
-  if (src && count) PK_HIP(c, hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-  return 0;
-}
 
 namespace {
 
 size_t cg_len(const pk_ctx* c) { return (size_t)std::max(std::max(c->n, c->m), 1); }
 
-// the context's work vectors [r | z | p | q | t] and the record, on first use
-int cg_state(pk_ctx* c, const char* who) {
-  int rc;
-  if ((rc = cg_reserve(c, c->cg.d_work, c->cg.work_cap, 5 * cg_len(c), who, "work vectors"))) return rc;
-  return cg_reserve(c, c->cg.d_rec, c->cg.rec_cap, PK_CG_REC, who, "the record");
-}
-
+// the context's work vectors and the record, on first use
 struct CgWork {
   double *r, *z, *p, *q, *t;
 };
-CgWork cg_work(const pk_ctx* c) {
-  const size_t L = cg_len(c);
-  double* w = c->cg.d_work;
-  return {w, w + L, w + 2 * L, w + 3 * L, w + 4 * L};
-}
+int cg_state(pk_ctx* c, const char* who) { return solve_state(c, c->cg, sizeof(CgWork) / sizeof(double*) * cg_len(c), PK_CG_REC, who); }
+CgWork cg_work(const pk_ctx* c) { return lib_slices<CgWork>(c->cg.d_work, cg_len(c)); }
 
 // what every entry point that applies K checks before anything is enqueued
 int cg_form_ready(pk_ctx* c, int form, bool with_h, bool pointers, const char* who) {
-  int rc;
   if (form < 0 || form > 1) return fail(c, 133, "%s: form must be 0 (primal) or 1 (dual)", who);
   if (form == 1 && with_h) return fail(c, 133, "%s: the dual form (1) has no Hessian term", who);
-  if (c->shard.flags || c->exchange.world > 1) return fail(c, 119, "%s: not offered for a sharded context", who);
-  if ((rc = op_ready(c, 0, pointers, who)) || (rc = op_ready(c, 1, pointers, who))) return rc;
-  return with_h ? op_ready(c, 2, pointers, who) : 0;
+  return solve_ops_ready(c, with_h, pointers, who);
 }
 
 int cg_size(const pk_ctx* c, int form) { return form == 0 ? c->n : c->m; }
 
 int cg_launch_elem(pk_ctx* c, const PkCgArgs& a, hipStream_t st) {
-  if (a.len > 0) PK_LIB_LAUNCH(c, pk_cg_elem, cg_elem_host, lib_grid(cg_items(a.len)), st, a);
+  if (a.len > 0) PK_LIB_LAUNCH(c, pk_cg_elem, cg_elem_host, lib_grid(lib_elem_items(a.len)), st, a);
   return 0;
 }
 
@@ -378,7 +286,7 @@ int cg_launch_scalar(pk_ctx* c, PkCgArgs a, int kind, int planes, hipStream_t st
 // one vector step on explicit pointers; the partials are reserved by the caller
 int cg_step(pk_ctx* c, int step, const PkCgArgs& in, hipStream_t st) {
   PkCgArgs a = in;
-  a.n_pieces = cg_pieces(a.len);
+  a.n_pieces = lib_dot_pieces(a.len);
   a.partial = c->cg.d_partial;
   a.kind = step;
   const unsigned grid = lib_grid(a.n_pieces);
@@ -397,9 +305,7 @@ int cg_step(pk_ctx* c, int step, const PkCgArgs& in, hipStream_t st) {
   }
 }
 
-int cg_reserve_partial(pk_ctx* c, int64_t len, const char* who) {
-  return cg_reserve(c, c->cg.d_partial, c->cg.partial_cap, (size_t)PK_CG_PLANES * (size_t)cg_pieces(len), who, "partial sums");
-}
+int cg_reserve_partial(pk_ctx* c, int64_t len, const char* who) { return solve_partial(c, c->cg, PK_CG_PLANES, len, who); }
 
 // steps 2 ... 5 of one application: q already holds s o v (or 0.0).  Checked by the caller: nothing here refuses.
 int cg_products(pk_ctx* c, int form, const double* jvals, const double* hvals, const double* d, const double* v, double* q, double* t,
@@ -435,25 +341,10 @@ int cg_iteration(pk_ctx* c, hipStream_t st) {
   return cg_step(c, PK_CG_DIRECTION, a, st);
 }
 
-// the host forms' scratch [b | x0 | x | d | s | minv | v] of max(n, m) doubles each
+// the host forms' scratch, max(n, m) doubles each
 struct CgScratch {
   double *b, *x0, *x, *d, *s, *minv, *v;
 };
-int cg_scratch(pk_ctx* c, CgScratch& s, const char* who) {
-  const size_t L = cg_len(c);
-  if (const int rc = cg_reserve(c, c->cg.d_scratch, c->cg.scratch_cap, 7 * L, who, "host-form scratch")) return rc;
-  double* w = c->cg.d_scratch;
-  s = {w, w + L, w + 2 * L, w + 3 * L, w + 4 * L, w + 5 * L, w + 6 * L};
-  return 0;
-}
-
-// the values pk_linearize left, for the host forms (error 118)
-int cg_linearized(pk_ctx* c, bool with_h, const double*& jvals, const double*& hvals, const char* who) {
-  int rc;
-  hvals = nullptr;
-  if ((rc = op_linearized(c, 0, jvals, who))) return rc;
-  return with_h ? op_linearized(c, 2, hvals, who) : 0;
-}
 
 }  // namespace
 
@@ -466,7 +357,7 @@ int pk_cg_step_dev(pk_ctx* c, int step, int64_t len, const double* d_b, const do
   const char* who = "pk_cg_step";
   if (step < PK_CG_INIT || step > PK_CG_JACOBI) return fail(c, 134, "%s: step must be 0 ... 5", who);
   if (len < 0) return fail(c, 134, "%s: length %lld", who, (long long)len);
-  if (step == PK_CG_INIT && !(tol >= 0.0 && __builtin_isfinite(tol))) return fail(c, 134, "%s: tol must be finite and not negative", who);
+  if (step == PK_CG_INIT && !solve_tol_ok(tol)) return fail(c, 134, "%s: tol must be finite and not negative", who);
   bool ok = true;
   switch (step) {
     case PK_CG_INIT: ok = d_b && d_x && d_r && d_z && d_p && d_q && d_rec; break;
@@ -497,11 +388,11 @@ int pk_condensed_apply(pk_ctx* c, int form, int with_h, const double* d, const d
   const double *jvals = nullptr, *hvals = nullptr;
   CgScratch w;
   int rc = host_ready(c, v && y);
-  if (rc || (rc = cg_form_ready(c, form, with_h != 0, true, who)) || (rc = cg_linearized(c, with_h != 0, jvals, hvals, who))) return rc;
-  if ((rc = cg_state(c, who)) || (rc = cg_scratch(c, w, who))) return rc;
+  if (rc || (rc = cg_form_ready(c, form, with_h != 0, true, who)) || (rc = solve_linearized(c, with_h != 0, jvals, hvals, who))) return rc;
+  if ((rc = cg_state(c, who)) || (rc = solve_scratch(c, c->cg, cg_len(c), w, who))) return rc;
   const size_t N = (size_t)cg_size(c, form), M = (size_t)cg_size(c, 1 - form);
   PK_HIP(c, hipSetDevice(c->device));
-  if ((rc = cg_up(c, w.v, v, N)) || (rc = cg_up(c, w.d, d, M)) || (rc = cg_up(c, w.s, s, N))) return rc;
+  if ((rc = lib_upload(c, w.v, v, N)) || (rc = lib_upload(c, w.d, d, M)) || (rc = lib_upload(c, w.s, s, N))) return rc;
   if ((rc = cg_apply(c, form, jvals, hvals, d ? w.d : nullptr, s ? w.s : nullptr, w.v, w.x, c->stream))) return rc;
   if (N) PK_HIP(c, hipMemcpyAsync(y, w.x, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
   PK_HIP(c, hipStreamSynchronize(c->stream));
@@ -513,13 +404,13 @@ int pk_cg_begin_dev(pk_ctx* c, int form, const double* d_jvals, const double* d_
   const char* who = "pk_cg_begin";
   int rc = ready(c);
   if (rc || (rc = cg_form_ready(c, form, d_hvals != nullptr, d_jvals && d_b && d_x, who))) return rc;
-  if (!(tol >= 0.0 && __builtin_isfinite(tol))) return fail(c, 134, "%s: tol must be finite and not negative", who);
+  if (!solve_tol_ok(tol)) return fail(c, 134, "%s: tol must be finite and not negative", who);
   const int64_t N = cg_size(c, form);
   if ((rc = cg_state(c, who)) || (rc = cg_reserve_partial(c, N, who))) return rc;
   hipStream_t st = pick(c, stream);
   const CgWork w = cg_work(c);
   PkCg& g = c->cg;
-  cg_forget(c);
+  solve_forget(g);
   if (d_x0 && (rc = cg_apply(c, form, d_jvals, d_hvals, d_d, d_s, d_x0, w.q, st))) return rc;
   PkCgArgs a{};
   a.b = d_b; a.x0 = d_x0; a.minv = d_minv; a.s = d_s; a.x = d_x; a.r = w.r; a.z = w.z; a.p = w.p; a.q = w.q; a.rec = g.d_rec;
@@ -531,26 +422,13 @@ int pk_cg_begin_dev(pk_ctx* c, int form, const double* d_jvals, const double* d_
 }
 
 int pk_cg_advance_dev(pk_ctx* c, int iters, void* stream) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (iters < 1) return fail(c, 134, "pk_cg_advance: iters = %d, at least one iteration", iters);
-  if (!c->cg.active) return fail(c, 135, "pk_cg_advance: no solve in progress (pk_cg_begin_dev)");
-  hipStream_t st = pick(c, stream);
-  c->cg.stream = st;
-  for (int k = 0; k < iters; ++k)
-    if ((rc = cg_iteration(c, st))) return rc;
-  return 0;
+  if (const int rc = ready(c)) return rc;
+  return solve_advance(c, c->cg, iters, stream, cg_iteration, "pk_cg_advance", "pk_cg_begin_dev");
 }
 
 int pk_cg_record(pk_ctx* c, double* rec) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (!rec) return fail(c, 60, "null host buffer");
-  if (!c->cg.active) return fail(c, 135, "pk_cg_record: no solve in progress (pk_cg_begin_dev)");
-  PK_HIP(c, hipSetDevice(c->device));
-  PK_HIP(c, hipMemcpyAsync(rec, c->cg.d_rec, sizeof(double) * PK_CG_REC, hipMemcpyDeviceToHost, c->cg.stream));
-  PK_HIP(c, hipStreamSynchronize(c->cg.stream));
-  return 0;
+  if (const int rc = ready(c)) return rc;
+  return solve_record(c, c->cg, rec, PK_CG_REC, "pk_cg_record", "pk_cg_begin_dev");
 }
 
 int pk_solve_condensed(pk_ctx* c, int form, int with_h, const double* d, const double* s, int precond, const double* minv,
@@ -560,18 +438,14 @@ int pk_solve_condensed(pk_ctx* c, int form, int with_h, const double* d, const d
   CgScratch w;
   int rc = host_ready(c, b && x && rec && (precond != 2 || minv));
   if (rc || (rc = cg_form_ready(c, form, with_h != 0, true, who))) return rc;
-  if (!(tol >= 0.0 && __builtin_isfinite(tol)) || maxiter < 1 || check_every < 1 || precond < 0 || precond > 2)
-    return fail(c, 134, "%s: tol %g (finite, not negative), maxiter %d and check_every %d (at least 1), precond %d (0, 1 or 2)", who, tol,
-                maxiter, check_every, precond);
-  if ((rc = cg_linearized(c, with_h != 0, jvals, hvals, who))) return rc;
-  if (precond == 1 && with_h && !c->ops.d_diag_pos) return fail(c, 132, "%s: call pk_set_operator_diagonal(2) first", who);
+  if ((rc = solve_host_checks(c, with_h != 0, tol, maxiter, check_every, precond, jvals, hvals, who))) return rc;
   const size_t N = (size_t)cg_size(c, form), M = (size_t)cg_size(c, 1 - form);
-  if ((rc = cg_state(c, who)) || (rc = cg_scratch(c, w, who)) || (rc = cg_reserve_partial(c, (int64_t)N, who))) return rc;
+  if ((rc = cg_state(c, who)) || (rc = solve_scratch(c, c->cg, cg_len(c), w, who)) || (rc = cg_reserve_partial(c, (int64_t)N, who))) return rc;
   PK_HIP(c, hipSetDevice(c->device));
-  if ((rc = cg_up(c, w.b, b, N)) || (rc = cg_up(c, w.x0, x0, N)) || (rc = cg_up(c, w.d, d, M)) || (rc = cg_up(c, w.s, s, N))) return rc;
+  if ((rc = lib_upload(c, w.b, b, N)) || (rc = lib_upload(c, w.x0, x0, N)) || (rc = lib_upload(c, w.d, d, M)) || (rc = lib_upload(c, w.s, s, N))) return rc;
   const double *dd = d ? w.d : nullptr, *ds = s ? w.s : nullptr, *dm = nullptr;
   if (precond == 2) {
-    if ((rc = cg_up(c, w.minv, minv, N))) return rc;
+    if ((rc = lib_upload(c, w.minv, minv, N))) return rc;
     dm = w.minv;
   } else if (precond == 1) {      // g = diag(K) without s, then minv = 1 / |g + s|
     if (with_h && (rc = pk_operator_diagonal_dev(c, 2, hvals, nullptr, w.minv, nullptr))) return rc;
@@ -582,16 +456,7 @@ int pk_solve_condensed(pk_ctx* c, int form, int with_h, const double* d, const d
     dm = w.minv;
   }
   if ((rc = pk_cg_begin_dev(c, form, jvals, hvals, dd, ds, dm, w.b, x0 ? w.x0 : nullptr, w.x, tol, nullptr))) return rc;
-  if ((rc = pk_cg_record(c, rec))) return rc;
-  for (int done = 0; rec[CG_STATUS] == 0.0 && done < maxiter;) {
-    const int chunk = std::min(check_every, maxiter - done);
-    if ((rc = pk_cg_advance_dev(c, chunk, nullptr)) || (rc = pk_cg_record(c, rec))) return rc;
-    done += chunk;
-  }
-  if (rec[CG_STATUS] == 0.0) rec[CG_STATUS] = 4.0;      // exhausted: in the host copy only
-  if (N) PK_HIP(c, hipMemcpyAsync(x, w.x, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return solve_host_loop(c, maxiter, check_every, pk_cg_advance_dev, pk_cg_record, rec, x, w.x, N);
 }
 
 }  // extern "C"

@@ -218,25 +218,6 @@ void free_merit(pk_ctx* c) {
 
 namespace {
 
-// An array of the context that grows when needed and never shrinks.  The new one is allocated first: error 127 enqueues
-// nothing and leaves what was there.  Work enqueued earlier may still use the old one, so the device is waited for.
-int merit_reserve(pk_ctx* c, double*& p, size_t& cap, size_t want, const char* who, const char* what) {
-  if (want <= cap) return 0;
-  PK_HIP(c, hipSetDevice(c->device));
-  double* q = nullptr;
-  if (hipMalloc((void**)&q, sizeof(double) * want) != hipSuccess || !q)
-    return fail(c, 127, "%s: no device memory for %zu doubles of %s", who, want, what);
-  const hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    release(q);
-    return fail(c, 100 + (int)e, "hipDeviceSynchronize failed: %s", hipGetErrorString(e));
-  }
-  release(p);
-  p = q;
-  cap = want;
-  return 0;
-}
-
 // entries of one chunk of the host forms: what bounds their scratch
 int64_t merit_chunk(const pk_ctx* c) {
   const int64_t per_entry = 8 * (c->nnz_J + (int64_t)c->n + c->m + 1);
@@ -265,11 +246,11 @@ int merit_host_form(pk_ctx* c, int64_t B, const double* x, const double* d, cons
   const size_t n = (size_t)c->n, m = (size_t)c->m, nj = (size_t)c->nnz_J;
   const size_t cap = (size_t)std::min<int64_t>(B, merit_chunk(c));
   PK_HIP(c, hipSetDevice(c->device));
-  if ((rc = merit_reserve(c, c->merit.d_scratch, c->merit.scratch_cap, 2 * n + cap * (2 * n + m + nj + 1 + PK_MERIT_COLS), who,
-                          "scratch")))
+  if ((rc = lib_reserve(c, c->merit.d_scratch, c->merit.scratch_cap, 2 * n + cap * (2 * n + m + nj + 1 + PK_MERIT_COLS), 127, who,
+                        "scratch")))
     return rc;
-  if ((rc = merit_reserve(c, c->merit.d_partial, c->merit.partial_cap,
-                          cap * (size_t)merit_pieces(c->m, c->n) * PK_MERIT_COLS, who, "partial rows")))
+  if ((rc = lib_reserve(c, c->merit.d_partial, c->merit.partial_cap, cap * (size_t)merit_pieces(c->m, c->n) * PK_MERIT_COLS, 127, who,
+                        "partial rows")))
     return rc;
   MeritScratch s;
   s.x = c->merit.d_scratch; s.d = s.x + n; s.X = s.d + n; s.f = s.X + cap * n; s.grad = s.f + cap; s.g = s.grad + cap * n;
@@ -362,8 +343,8 @@ int pk_merit_reduce_dev(pk_ctx* c, int B, int64_t n_g, const double* d_g, int64_
   PkMeritArgs a{};
   a.g = d_g; a.clb = d_clb; a.cub = d_cub; a.X = d_X; a.vlb = d_vlb; a.vub = d_vub; a.grad = d_grad; a.d = d_d; a.f = d_f;
   a.out = d_out; a.ldg = ldg; a.ldx = ldx; a.ldgrad = ldgrad; a.n_g = n_g; a.n_x = n_x; a.n_pieces = merit_pieces(n_g, n_x); a.B = B;
-  if ((rc = merit_reserve(c, c->merit.d_partial, c->merit.partial_cap, (size_t)B * (size_t)a.n_pieces * PK_MERIT_COLS,
-                          "pk_merit_reduce", "partial rows")))
+  if ((rc = lib_reserve(c, c->merit.d_partial, c->merit.partial_cap, (size_t)B * (size_t)a.n_pieces * PK_MERIT_COLS, 127,
+                        "pk_merit_reduce", "partial rows")))
     return rc;
   a.partial = c->merit.d_partial;
   hipStream_t st = pick(c, stream);

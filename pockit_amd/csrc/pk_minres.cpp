@@ -51,14 +51,11 @@
 // iterations were enqueued beyond the stop.
 //
 // Every product is rounded before its sum: nothing here contracts to a fused multiply-add.  sqrt and / are the correctly
-// rounded ones.  The dots have the association of pk_merit.cpp and pk_cg.cpp (DESIGN.md sections 16, 18): index i belongs to
-// piece i / 2048; thread t of the piece adds the terms at piece * 2048 + t + 256 j, j = 0 ... 7, in ascending j to 0.0 (an index
-// beyond the length adds nothing); the 256 thread values meet in LDS and are reduced by the fixed tree of widths 128 ... 1
-// (slot t += slot t + w), one LDS plane per simultaneous dot (two in begin: b.Mb, r1.y; one in the dot and in the update);
-// partial[plane * n_pieces + piece].  The scalar step is one workgroup: thread t adds the pieces t, t + 256, ... in ascending
-// order to 0.0, the same tree follows, thread 0 does the arithmetic above.  n_pieces = max(1, ceil(len / 2048)).  No atomics, no
-// dependence on the grid, the same bits from run to run.  The work item of begin, the dot and the update is a piece; the
-// elementwise kernels take 256 elements per item; the grid rule is lib_grid.
+// rounded ones.  The dots are the pieced dots of pk_libkernel.h (pieces of 2048, 8 terms per thread, the fixed tree, the
+// one-workgroup scalar step), one LDS plane per simultaneous dot: two in begin (b.Mb, r1.y), one in the dot and in the update.
+// The work item of begin, the dot and the update is a piece; the elementwise kernels take 256 elements per item; the grid rule
+// is lib_grid.  The host side of a solve -- the context's arrays, the checks, the skeletons of record / advance and of the
+// host form's loop -- is pk_solve.cpp's.
 //
 // The diagonal preconditioner built on the device (pk_solve_kkt, precond 1): g1 = diag H (pk_operator_diagonal_dev; 0.0 without
 // H), minv1 = recip |g1 + s1|; g2_i = sum_j J_ij^2 minv1_j (pk_operator_reduce_dev, sq_sum, w = minv1), minv2 = recip |g2 + s2|;
@@ -74,7 +71,7 @@
 
 #include "pk_libkernel.h"      // (behind the pragma: what its templates are instantiated with is this unit's arithmetic)
 
-enum { PK_MR_PER_THREAD = 8, PK_MR_PIECE = PK_BLOCK * PK_MR_PER_THREAD, PK_MR_PLANES = 2, PK_MR_REC = 16 };
+enum { PK_MR_PLANES = 2, PK_MR_REC = 16 };
 enum { MR_STATUS = 0, MR_ITERS = 1, MR_PHIBAR = 2, MR_THR = 3, MR_BETA = 4, MR_OLDB = 5, MR_ALFA = 6, MR_DBAR = 7, MR_EPSLN = 8,
        MR_CS = 9, MR_SN = 10, MR_PHI = 11, MR_OLDEPS = 12, MR_DELTA = 13, MR_GAMMA = 14, MR_FRESH = 15 };
 enum { PK_MR_INIT = 0, PK_MR_LANCZOS = 1, PK_MR_ALFA = 2, PK_MR_UPDATE = 3, PK_MR_SOLUTION = 4, PK_MR_DIAG = 5, PK_MR_RECIP = 6 };
@@ -94,14 +91,11 @@ struct PkMrScalars {
   double c0, c1, c2, c3;
 };
 
-static int64_t mr_pieces(int64_t len) { return std::max<int64_t>(1, (len + PK_MR_PIECE - 1) / PK_MR_PIECE); }
-static int64_t mr_items(int64_t len) { return (len + PK_BLOCK - 1) / PK_BLOCK; }
-
 // ---------------------------------------------------------------- thread t of piece pc: its elements, its terms into the planes
 PK_LIB_FN void mr_init_thread(const PkMrArgs& a, int64_t pc, int t, double* s) {
   double bmb = 0.0, ry = 0.0;
-  for (int j = 0; j < PK_MR_PER_THREAD; ++j) {
-    const int64_t i = pc * PK_MR_PIECE + t + (int64_t)PK_BLOCK * j;
+  for (int j = 0; j < PK_LIB_PER_THREAD; ++j) {
+    const int64_t i = pc * PK_LIB_PIECE + t + (int64_t)PK_BLOCK * j;
     if (i < a.len) {
       const double bi = a.b[i];
       const double ri = a.x0 ? bi - a.q[i] : bi;      // (with x0 the application left K x0 in q)
@@ -123,8 +117,8 @@ PK_LIB_FN void mr_init_thread(const PkMrArgs& a, int64_t pc, int t, double* s) {
 
 PK_LIB_FN void mr_dot_thread(const PkMrArgs& a, int64_t pc, int t, double* s) {
   double vq = 0.0;
-  for (int j = 0; j < PK_MR_PER_THREAD; ++j) {
-    const int64_t i = pc * PK_MR_PIECE + t + (int64_t)PK_BLOCK * j;
+  for (int j = 0; j < PK_LIB_PER_THREAD; ++j) {
+    const int64_t i = pc * PK_LIB_PIECE + t + (int64_t)PK_BLOCK * j;
     if (i < a.len) {
       const double term = a.v[i] * a.q[i];
       vq = vq + term;
@@ -144,8 +138,8 @@ PK_LIB_FN PkMrScalars mr_update_scalars(const double* rec) {
 
 PK_LIB_FN void mr_update_thread(const PkMrArgs& a, int64_t pc, int t, const PkMrScalars& k, double* s) {
   double ty = 0.0;
-  for (int j = 0; j < PK_MR_PER_THREAD; ++j) {
-    const int64_t i = pc * PK_MR_PIECE + t + (int64_t)PK_BLOCK * j;
+  for (int j = 0; j < PK_LIB_PER_THREAD; ++j) {
+    const int64_t i = pc * PK_LIB_PIECE + t + (int64_t)PK_BLOCK * j;
     if (i < a.len) {
       const double r2 = a.r2[i];
       double ti = a.q[i];
@@ -164,26 +158,6 @@ PK_LIB_FN void mr_update_thread(const PkMrArgs& a, int64_t pc, int t, const PkMr
     }
   }
   s[t] = ty;
-}
-
-// one step of the trees of `planes` dots, which share the barrier of the level: widths 128, 64 ... 1
-PK_LIB_FN void mr_tree_step(double* s, int w, int t, int planes) {
-  if (t >= w) return;
-  for (int q = 0; q < planes; ++q) s[q * PK_BLOCK + t] = s[q * PK_BLOCK + t] + s[q * PK_BLOCK + t + w];
-}
-
-// thread q < planes behind the trees
-PK_LIB_FN void mr_store_partial(const PkMrArgs& a, int64_t pc, int q, const double* s) {
-  a.partial[(int64_t)q * a.n_pieces + pc] = s[q * PK_BLOCK];
-}
-
-// thread t of the scalar step: per plane the pieces t, t + 256, ... in ascending order
-PK_LIB_FN void mr_scalar_thread(const PkMrArgs& a, int t, double* s) {
-  for (int q = 0; q < a.planes; ++q) {
-    double acc = 0.0;
-    for (int64_t pc = t; pc < a.n_pieces; pc += PK_BLOCK) acc = acc + a.partial[(int64_t)q * a.n_pieces + pc];
-    s[q * PK_BLOCK + t] = acc;
-  }
 }
 
 // thread 0 of the scalar step behind the trees: plane q ended in s[q * PK_BLOCK]
@@ -303,8 +277,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_mr_init(PkMrArgs a) {
   for (int64_t pc = (int64_t)blockIdx.x; pc < a.n_pieces; pc += (int64_t)gridDim.x) {
     mr_init_thread(a, pc, t, s);
     __syncthreads();
-    lib_tree(mr_tree_step, s, t, 2);
-    if (t < 2) mr_store_partial(a, pc, t, s);
+    lib_tree(lib_planes_step, s, t, 2);
+    if (t < 2) lib_store_partial(a, pc, t, s);
     __syncthreads();          // the next piece of this workgroup's stride overwrites the planes
   }
 }
@@ -315,8 +289,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_mr_dot(PkMrArgs a) {
   for (int64_t pc = (int64_t)blockIdx.x; pc < a.n_pieces; pc += (int64_t)gridDim.x) {
     mr_dot_thread(a, pc, t, s);
     __syncthreads();
-    lib_tree(mr_tree_step, s, t, 1);
-    if (t < 1) mr_store_partial(a, pc, t, s);
+    lib_tree(lib_planes_step, s, t, 1);
+    if (t < 1) lib_store_partial(a, pc, t, s);
     __syncthreads();
   }
 }
@@ -329,8 +303,8 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_mr_update(PkMrArgs a) {
   for (int64_t pc = (int64_t)blockIdx.x; pc < a.n_pieces; pc += (int64_t)gridDim.x) {
     mr_update_thread(a, pc, t, k, s);
     __syncthreads();
-    lib_tree(mr_tree_step, s, t, 1);
-    if (t < 1) mr_store_partial(a, pc, t, s);
+    lib_tree(lib_planes_step, s, t, 1);
+    if (t < 1) lib_store_partial(a, pc, t, s);
     __syncthreads();
   }
 }
@@ -338,9 +312,9 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_mr_update(PkMrArgs a) {
 __global__ void __launch_bounds__(PK_BLOCK) pk_mr_scalar(PkMrArgs a) {
   __shared__ double s[PK_MR_PLANES * PK_BLOCK];
   const int t = (int)threadIdx.x;
-  mr_scalar_thread(a, t, s);
+  lib_scalar_thread(a, t, s);
   __syncthreads();
-  lib_tree(mr_tree_step, s, t, a.planes);
+  lib_tree(lib_planes_step, s, t, a.planes);
   if (t == 0) mr_scalar_decide(a, s);
 }
 
@@ -352,84 +326,38 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_mr_elem(PkMrArgs a) {
 }
 #else
 // ---------------------------------------------------------------- host stand-in: the identical walk
-template <class Thread>
-static void mr_pieces_host(const PkMrArgs& a, unsigned grid, int planes, Thread thread) {
-  double s[PK_MR_PLANES * PK_BLOCK];
-  lib_walk_host(grid, a.n_pieces, [&](int64_t pc) {
-    for (int t = 0; t < PK_BLOCK; ++t) thread(pc, t, s);
-    lib_tree_host(mr_tree_step, s, planes);
-    for (int q = 0; q < planes; ++q) mr_store_partial(a, pc, q, s);
-  });
-}
-
 static void mr_init_host(const PkMrArgs& a, unsigned grid) {
-  mr_pieces_host(a, grid, 2, [&](int64_t pc, int t, double* s) { mr_init_thread(a, pc, t, s); });
+  lib_pieces_host<PK_MR_PLANES>(a, grid, 2, [&](int64_t pc, int t, double* s) { mr_init_thread(a, pc, t, s); });
 }
 static void mr_dot_host(const PkMrArgs& a, unsigned grid) {
-  mr_pieces_host(a, grid, 1, [&](int64_t pc, int t, double* s) { mr_dot_thread(a, pc, t, s); });
+  lib_pieces_host<PK_MR_PLANES>(a, grid, 1, [&](int64_t pc, int t, double* s) { mr_dot_thread(a, pc, t, s); });
 }
 static void mr_update_host(const PkMrArgs& a, unsigned grid) {
   if (a.rec[MR_STATUS] != 0.0) return;
   const PkMrScalars k = mr_update_scalars(a.rec);
-  mr_pieces_host(a, grid, 1, [&](int64_t pc, int t, double* s) { mr_update_thread(a, pc, t, k, s); });
+  lib_pieces_host<PK_MR_PLANES>(a, grid, 1, [&](int64_t pc, int t, double* s) { mr_update_thread(a, pc, t, k, s); });
 }
-static void mr_scalar_host(const PkMrArgs& a, unsigned) {
-  double s[PK_MR_PLANES * PK_BLOCK];
-  for (int t = 0; t < PK_BLOCK; ++t) mr_scalar_thread(a, t, s);
-  lib_tree_host(mr_tree_step, s, (int)a.planes);
-  mr_scalar_decide(a, s);
-}
+static void mr_scalar_host(const PkMrArgs& a, unsigned) { lib_scalar_host<PK_MR_PLANES>(a, mr_scalar_decide); }
 static void mr_elem_host(const PkMrArgs& a, unsigned grid) {
   const PkMrScalars k = mr_elem_scalars(a);
   if (a.kind == PK_MR_SOLUTION && !k.on) return;
-  lib_walk_host(grid, mr_items(a.len), [&](int64_t item) {
-    for (int64_t i = item * PK_BLOCK; i < std::min<int64_t>(a.len, (item + 1) * PK_BLOCK); ++i) mr_element(a, i, k);
-  });
+  lib_elements_host(grid, a.len, [&](int64_t i) { mr_element(a, i, k); });
 }
 #endif
-
-void minres_forget(pk_ctx* c) {
-  PkMinres& g = c->minres;
-  g.active = false;
-  g.jvals = g.hvals = g.s1 = g.s2 = g.minv = nullptr;
-  g.x = nullptr;
-}
-
-void free_minres(pk_ctx* c) {
-  release(c->minres.d_work); release(c->minres.d_partial); release(c->minres.d_rec); release(c->minres.d_scratch);
-  c->minres = PkMinres{};
-}
 
 namespace {
 
 size_t mr_len(const pk_ctx* c) { return (size_t)std::max(c->n + c->m, 1); }
 
-// the context's work vectors [r1 | r2 | y | v | w | w2 | q] and the record, on first use
-int mr_state(pk_ctx* c, const char* who) {
-  int rc;
-  if ((rc = cg_reserve(c, c->minres.d_work, c->minres.work_cap, 7 * mr_len(c), who, "work vectors"))) return rc;
-  return cg_reserve(c, c->minres.d_rec, c->minres.rec_cap, PK_MR_REC, who, "the record");
-}
-
+// the context's work vectors and the record, on first use
 struct MrWork {
   double *r1, *r2, *y, *v, *w, *w2, *q;
 };
-MrWork mr_work(const pk_ctx* c) {
-  const size_t L = mr_len(c);
-  double* w = c->minres.d_work;
-  return {w, w + L, w + 2 * L, w + 3 * L, w + 4 * L, w + 5 * L, w + 6 * L};
-}
-
-// what every entry point that applies K checks before anything is enqueued
-int mr_ready(pk_ctx* c, bool with_h, bool pointers, const char* who) {
-  int rc;
-  if (c->shard.flags || c->exchange.world > 1) return fail(c, 119, "%s: not offered for a sharded context", who);
-  if ((rc = op_ready(c, 0, pointers, who)) || (rc = op_ready(c, 1, pointers, who))) return rc;
-  return with_h ? op_ready(c, 2, pointers, who) : 0;
-}
+int mr_state(pk_ctx* c, const char* who) { return solve_state(c, c->minres, sizeof(MrWork) / sizeof(double*) * mr_len(c), PK_MR_REC, who); }
+MrWork mr_work(const pk_ctx* c) { return lib_slices<MrWork>(c->minres.d_work, mr_len(c)); }
 
 int mr_launch_elem(pk_ctx* c, const PkMrArgs& a, hipStream_t st) {
-  if (a.len > 0) PK_LIB_LAUNCH(c, pk_mr_elem, mr_elem_host, lib_grid(mr_items(a.len)), st, a);
+  if (a.len > 0) PK_LIB_LAUNCH(c, pk_mr_elem, mr_elem_host, lib_grid(lib_elem_items(a.len)), st, a);
   return 0;
 }
 
@@ -442,7 +370,7 @@ int mr_launch_scalar(pk_ctx* c, PkMrArgs a, int kind, int planes, hipStream_t st
 // one vector step on explicit pointers; the partials are reserved by the caller
 int mr_step(pk_ctx* c, int step, const PkMrArgs& in, hipStream_t st) {
   PkMrArgs a = in;
-  a.n_pieces = mr_pieces(a.len);
+  a.n_pieces = lib_dot_pieces(a.len);
   a.partial = c->minres.d_partial;
   a.kind = step;
   const unsigned grid = lib_grid(a.n_pieces);
@@ -461,9 +389,7 @@ int mr_step(pk_ctx* c, int step, const PkMrArgs& in, hipStream_t st) {
   }
 }
 
-int mr_reserve_partial(pk_ctx* c, int64_t len, const char* who) {
-  return cg_reserve(c, c->minres.d_partial, c->minres.partial_cap, (size_t)PK_MR_PLANES * (size_t)mr_pieces(len), who, "partial sums");
-}
+int mr_reserve_partial(pk_ctx* c, int64_t len, const char* who) { return solve_partial(c, c->minres, PK_MR_PLANES, len, who); }
 
 // steps 2 ... 4 of one application: q already holds the diagonal blocks' terms.  Checked by the caller: nothing here refuses.
 int mr_products(pk_ctx* c, const double* jvals, const double* hvals, const double* v, double* q, hipStream_t st) {
@@ -495,27 +421,10 @@ int mr_iteration(pk_ctx* c, hipStream_t st) {
   return mr_step(c, PK_MR_SOLUTION, a, st);
 }
 
-// the host forms' scratch [b | x0 | x | s1 s2 | minv | v] of n + m doubles each
+// the host forms' scratch, n + m doubles each (s: s1 | s2)
 struct MrScratch {
   double *b, *x0, *x, *s, *minv, *v;
 };
-int mr_scratch(pk_ctx* c, MrScratch& s, const char* who) {
-  const size_t L = mr_len(c);
-  if (const int rc = cg_reserve(c, c->minres.d_scratch, c->minres.scratch_cap, 6 * L, who, "host-form scratch")) return rc;
-  double* w = c->minres.d_scratch;
-  s = {w, w + L, w + 2 * L, w + 3 * L, w + 4 * L, w + 5 * L};
-  return 0;
-}
-
-// the values pk_linearize left, for the host forms (error 118)
-int mr_linearized(pk_ctx* c, bool with_h, const double*& jvals, const double*& hvals, const char* who) {
-  int rc;
-  hvals = nullptr;
-  if ((rc = op_linearized(c, 0, jvals, who))) return rc;
-  return with_h ? op_linearized(c, 2, hvals, who) : 0;
-}
-
-bool mr_tol_ok(double tol) { return tol >= 0.0 && __builtin_isfinite(tol); }
 
 }  // namespace
 
@@ -529,7 +438,7 @@ int pk_minres_step_dev(pk_ctx* c, int step, int64_t len, int64_t split, const do
   const char* who = "pk_minres_step";
   if (step < PK_MR_INIT || step > PK_MR_RECIP) return fail(c, 134, "%s: step must be 0 ... 6", who);
   if (len < 0 || split < 0 || split > len) return fail(c, 134, "%s: length %lld, split %lld", who, (long long)len, (long long)split);
-  if (step == PK_MR_INIT && !mr_tol_ok(tol)) return fail(c, 134, "%s: tol must be finite and not negative", who);
+  if (step == PK_MR_INIT && !solve_tol_ok(tol)) return fail(c, 134, "%s: tol must be finite and not negative", who);
   bool ok = true;
   switch (step) {
     case PK_MR_INIT: ok = d_b && d_x && d_r1 && d_r2 && d_y && d_w && d_w2 && d_rec && (!d_x0 || d_q); break;
@@ -551,7 +460,7 @@ int pk_minres_step_dev(pk_ctx* c, int step, int64_t len, int64_t split, const do
 int pk_kkt_apply_dev(pk_ctx* c, const double* d_jvals, const double* d_hvals, const double* d_s1, const double* d_s2, const double* d_v,
                      double* d_y, void* stream) {
   int rc = ready(c);
-  if (rc || (rc = mr_ready(c, d_hvals != nullptr, d_jvals && d_v && d_y, "pk_kkt_apply"))) return rc;
+  if (rc || (rc = solve_ops_ready(c, d_hvals != nullptr, d_jvals && d_v && d_y, "pk_kkt_apply"))) return rc;
   return mr_apply(c, d_jvals, d_hvals, d_s1, d_s2, d_v, d_y, pick(c, stream));
 }
 
@@ -560,11 +469,11 @@ int pk_kkt_apply(pk_ctx* c, int with_h, const double* s1, const double* s2, cons
   const double *jvals = nullptr, *hvals = nullptr;
   MrScratch w;
   int rc = host_ready(c, v && y);
-  if (rc || (rc = mr_ready(c, with_h != 0, true, who)) || (rc = mr_linearized(c, with_h != 0, jvals, hvals, who))) return rc;
-  if ((rc = mr_scratch(c, w, who))) return rc;
+  if (rc || (rc = solve_ops_ready(c, with_h != 0, true, who)) || (rc = solve_linearized(c, with_h != 0, jvals, hvals, who))) return rc;
+  if ((rc = solve_scratch(c, c->minres, mr_len(c), w, who))) return rc;
   const size_t n = (size_t)c->n, m = (size_t)c->m, N = n + m;
   PK_HIP(c, hipSetDevice(c->device));
-  if ((rc = cg_up(c, w.v, v, N)) || (rc = cg_up(c, w.s, s1, n)) || (rc = cg_up(c, w.s + n, s2, m))) return rc;
+  if ((rc = lib_upload(c, w.v, v, N)) || (rc = lib_upload(c, w.s, s1, n)) || (rc = lib_upload(c, w.s + n, s2, m))) return rc;
   if ((rc = mr_apply(c, jvals, hvals, s1 ? w.s : nullptr, s2 ? w.s + n : nullptr, w.v, w.x, c->stream))) return rc;
   if (N) PK_HIP(c, hipMemcpyAsync(y, w.x, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
   PK_HIP(c, hipStreamSynchronize(c->stream));
@@ -575,14 +484,14 @@ int pk_minres_begin_dev(pk_ctx* c, const double* d_jvals, const double* d_hvals,
                         const double* d_minv, const double* d_b, const double* d_x0, double* d_x, double tol, void* stream) {
   const char* who = "pk_minres_begin";
   int rc = ready(c);
-  if (rc || (rc = mr_ready(c, d_hvals != nullptr, d_jvals && d_b && d_x, who))) return rc;
-  if (!mr_tol_ok(tol)) return fail(c, 134, "%s: tol must be finite and not negative", who);
+  if (rc || (rc = solve_ops_ready(c, d_hvals != nullptr, d_jvals && d_b && d_x, who))) return rc;
+  if (!solve_tol_ok(tol)) return fail(c, 134, "%s: tol must be finite and not negative", who);
   const int64_t N = (int64_t)c->n + c->m;
   if ((rc = mr_state(c, who)) || (rc = mr_reserve_partial(c, N, who))) return rc;
   hipStream_t st = pick(c, stream);
   const MrWork w = mr_work(c);
   PkMinres& g = c->minres;
-  minres_forget(c);
+  solve_forget(g);
   if (d_x0 && (rc = mr_apply(c, d_jvals, d_hvals, d_s1, d_s2, d_x0, w.q, st))) return rc;
   PkMrArgs a{};
   a.b = d_b; a.x0 = d_x0; a.minv = d_minv; a.x = d_x; a.r1 = w.r1; a.r2 = w.r2; a.y = w.y; a.v = w.v; a.w = w.w; a.w2 = w.w2; a.q = w.q;
@@ -594,25 +503,13 @@ int pk_minres_begin_dev(pk_ctx* c, const double* d_jvals, const double* d_hvals,
 }
 
 int pk_minres_advance_dev(pk_ctx* c, int iters, void* stream) {
-  int rc = ready(c);
-  if (rc) return rc;
-  if (iters < 1) return fail(c, 134, "pk_minres_advance: iters = %d, at least one iteration", iters);
-  if (!c->minres.active) return fail(c, 135, "pk_minres_advance: no solve in progress (pk_minres_begin_dev)");
-  hipStream_t st = pick(c, stream);
-  c->minres.stream = st;
-  for (int k = 0; k < iters; ++k)
-    if ((rc = mr_iteration(c, st))) return rc;
-  return 0;
+  if (const int rc = ready(c)) return rc;
+  return solve_advance(c, c->minres, iters, stream, mr_iteration, "pk_minres_advance", "pk_minres_begin_dev");
 }
 
 int pk_minres_record(pk_ctx* c, double* rec) {
   int rc = ready(c);
-  if (rc) return rc;
-  if (!rec) return fail(c, 60, "null host buffer");
-  if (!c->minres.active) return fail(c, 135, "pk_minres_record: no solve in progress (pk_minres_begin_dev)");
-  PK_HIP(c, hipSetDevice(c->device));
-  PK_HIP(c, hipMemcpyAsync(rec, c->minres.d_rec, sizeof(double) * PK_MR_REC, hipMemcpyDeviceToHost, c->minres.stream));
-  PK_HIP(c, hipStreamSynchronize(c->minres.stream));
+  if (rc || (rc = solve_record(c, c->minres, rec, PK_MR_REC, "pk_minres_record", "pk_minres_begin_dev"))) return rc;
   rec[MR_FRESH] = 0.0;      // internal: between two iterations the solution update has always run
   return 0;
 }
@@ -623,19 +520,15 @@ int pk_solve_kkt(pk_ctx* c, int with_h, const double* s1, const double* s2, int 
   const double *jvals = nullptr, *hvals = nullptr;
   MrScratch w;
   int rc = host_ready(c, b && x && rec && (precond != 2 || minv));
-  if (rc || (rc = mr_ready(c, with_h != 0, true, who))) return rc;
-  if (!mr_tol_ok(tol) || maxiter < 1 || check_every < 1 || precond < 0 || precond > 2)
-    return fail(c, 134, "%s: tol %g (finite, not negative), maxiter %d and check_every %d (at least 1), precond %d (0, 1 or 2)", who, tol,
-                maxiter, check_every, precond);
-  if ((rc = mr_linearized(c, with_h != 0, jvals, hvals, who))) return rc;
-  if (precond == 1 && with_h && !c->ops.d_diag_pos) return fail(c, 132, "%s: call pk_set_operator_diagonal(2) first", who);
+  if (rc || (rc = solve_ops_ready(c, with_h != 0, true, who))) return rc;
+  if ((rc = solve_host_checks(c, with_h != 0, tol, maxiter, check_every, precond, jvals, hvals, who))) return rc;
   const size_t n = (size_t)c->n, m = (size_t)c->m, N = n + m;
-  if ((rc = mr_state(c, who)) || (rc = mr_scratch(c, w, who)) || (rc = mr_reserve_partial(c, (int64_t)N, who))) return rc;
+  if ((rc = mr_state(c, who)) || (rc = solve_scratch(c, c->minres, mr_len(c), w, who)) || (rc = mr_reserve_partial(c, (int64_t)N, who))) return rc;
   PK_HIP(c, hipSetDevice(c->device));
-  if ((rc = cg_up(c, w.b, b, N)) || (rc = cg_up(c, w.x0, x0, N)) || (rc = cg_up(c, w.s, s1, n)) || (rc = cg_up(c, w.s + n, s2, m))) return rc;
+  if ((rc = lib_upload(c, w.b, b, N)) || (rc = lib_upload(c, w.x0, x0, N)) || (rc = lib_upload(c, w.s, s1, n)) || (rc = lib_upload(c, w.s + n, s2, m))) return rc;
   const double *d1 = s1 ? w.s : nullptr, *d2 = s2 ? w.s + n : nullptr, *dm = nullptr;
   if (precond == 2) {
-    if ((rc = cg_up(c, w.minv, minv, N))) return rc;
+    if ((rc = lib_upload(c, w.minv, minv, N))) return rc;
     dm = w.minv;
   } else if (precond == 1) {      // minv1 = recip |diag H + s1|, then minv2 = recip |sum_j J_ij^2 minv1_j + s2|
     if (with_h && (rc = pk_operator_diagonal_dev(c, 2, hvals, nullptr, w.minv, nullptr))) return rc;
@@ -648,16 +541,7 @@ int pk_solve_kkt(pk_ctx* c, int with_h, const double* s1, const double* s2, int 
     dm = w.minv;
   }
   if ((rc = pk_minres_begin_dev(c, jvals, hvals, d1, d2, dm, w.b, x0 ? w.x0 : nullptr, w.x, tol, nullptr))) return rc;
-  if ((rc = pk_minres_record(c, rec))) return rc;
-  for (int done = 0; rec[MR_STATUS] == 0.0 && done < maxiter;) {
-    const int chunk = std::min(check_every, maxiter - done);
-    if ((rc = pk_minres_advance_dev(c, chunk, nullptr)) || (rc = pk_minres_record(c, rec))) return rc;
-    done += chunk;
-  }
-  if (rec[MR_STATUS] == 0.0) rec[MR_STATUS] = 4.0;      // exhausted: in the host copy only
-  if (N) PK_HIP(c, hipMemcpyAsync(x, w.x, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
-  PK_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return solve_host_loop(c, maxiter, check_every, pk_minres_advance_dev, pk_minres_record, rec, x, w.x, N);
 }
 
 }  // extern "C"

@@ -300,8 +300,8 @@ void free_operators(pk_ctx* c) {
   release(c->ops.d_v); release(c->ops.d_y); release(c->ops.d_diag_pos);
   c->ops.scratch_k = 0;
   c->ops.lin_J = c->ops.lin_H = nullptr;
-  cg_forget(c);      // (a solve in progress holds pointers into what the operators were built from)
-  minres_forget(c);
+  solve_forget(c->cg);      // (a solve in progress holds pointers into what the operators were built from)
+  solve_forget(c->minres);
 }
 
 void drop_linearization(pk_ctx* c) { c->ops.lin_J = c->ops.lin_H = nullptr; }
@@ -358,8 +358,8 @@ int pk_set_csr_operator(pk_ctx* c, int op, const int32_t* indptr, const int32_t*
   PK_HIP(c, hipStreamSynchronize(c->stream));
   PkOperator& o = c->ops.op[op];
   free_operator(o);
-  cg_forget(c);
-  minres_forget(c);
+  solve_forget(c->cg);
+  solve_forget(c->minres);
   if ((rc = upload(c, (void**)&o.d_indptr, indptr, sizeof(int32_t) * ((size_t)n_rows + 1)))) return rc;
   if ((rc = upload(c, (void**)&o.d_indices, indices, sizeof(int32_t) * (size_t)nnz))) return rc;
   if (src && (rc = upload(c, (void**)&o.d_src, src, sizeof(int32_t) * (size_t)nnz))) return rc;

@@ -13,13 +13,16 @@
 //   pk_merit.cpp    merit terms of a batch of trial points reduced on the device (pk_trial, pk_merit, pk_merit_fin: the library's
 //                   own kernels), the bounds they are measured against, the scratch of the host forms
 //   pk_cg.cpp       the condensed KKT matrix and the normal equations applied and solved by preconditioned CG on the device
-//                   (pk_cg_init, pk_cg_dot, pk_cg_update, pk_cg_scalar, pk_cg_elem: the library's own kernels), its work vectors
+//                   (pk_cg_init, pk_cg_dot, pk_cg_update, pk_cg_scalar, pk_cg_elem: the library's own kernels)
 //   pk_minres.cpp   the augmented (indefinite) KKT system applied and solved by preconditioned MINRES on the device
-//                   (pk_mr_init, pk_mr_dot, pk_mr_update, pk_mr_scalar, pk_mr_elem: the library's own kernels), its work vectors
+//                   (pk_mr_init, pk_mr_dot, pk_mr_update, pk_mr_scalar, pk_mr_elem: the library's own kernels)
+//   pk_solve.cpp    the host scaffolding of a device-resident solve, shared by the two units above: the context's growing arrays
+//                   (lib_reserve, also pk_merit.cpp's), the common checks, the skeletons of record / advance / the host loop
 //   pk_error.cpp    fail(): where an error message is kept
 //
-// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp and pk_minres.cpp share beyond it: the scaffolding of kernels that
-// are compiled into the library (function macro, tree driver, grid rule, host walk, launch).
+// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp and pk_minres.cpp share
+// beyond it: the scaffolding of kernels that are compiled into the library (function macro, tree driver, grid rule, host walk,
+// launch) and the pieced dot of the two solvers (piece size, tree step, partial store, scalar trip, their host stand-ins).
 //
 // Holds what they share: pk_ctx (one member per area, each with ONE reset function in the unit that owns it), PK_HIP, and the
 // few helpers that cross a unit boundary.  The helpers of the per-callback path are either defined in
@@ -166,41 +169,34 @@ struct PkMerit {
   size_t scratch_cap = 0;
 };
 
-// ---- CG on the condensed KKT matrix / the normal equations (pk_cg.cpp: pk_cg_begin_dev, pk_solve_condensed ...; free_cg, cg_forget)
+// ---- what a device-resident iterative solve keeps in the context, whichever the method (pk_solve.cpp; solve_free, solve_forget)
 // Allocated on first use; every array grows when needed and never shrinks short of pk_set_problem.
-struct PkCg {
-  double* d_work = nullptr;         // [r | z | p | q | t], max(n, m) doubles each
+struct PkSolveState {
+  double* d_work = nullptr;         // the method's work vectors, slices of one length
   size_t work_cap = 0;
-  double* d_partial = nullptr;      // the pieces' partial sums, 3 planes of n_pieces doubles
+  double* d_partial = nullptr;      // the pieces' partial sums, planes x n_pieces doubles (pk_libkernel.h)
   size_t partial_cap = 0;
-  double* d_rec = nullptr;          // the record of 8 doubles
+  double* d_rec = nullptr;          // the method's record
   size_t rec_cap = 0;
-  double* d_scratch = nullptr;      // the host forms' [b | x0 | x | d | s | minv | v], max(n, m) doubles each
+  double* d_scratch = nullptr;      // the host forms' copies of the caller's arrays, slices of the same length
   size_t scratch_cap = 0;
-  // the solve in progress (pk_cg_begin_dev): the caller's arrays; forgotten by pk_set_csr_operator and pk_set_csr_map
-  bool active = false;
-  int form = 0;
-  const double *jvals = nullptr, *hvals = nullptr, *d = nullptr, *s = nullptr, *minv = nullptr;
-  double* x = nullptr;
-  hipStream_t stream = nullptr;     // where the last begin / advance was enqueued: pk_cg_record copies behind it
+  bool active = false;              // a solve is in progress (begin): forgotten by pk_set_csr_operator and pk_set_csr_map
+  hipStream_t stream = nullptr;     // where the last begin / advance was enqueued: the record is copied behind it
 };
 
-// ---- MINRES on the augmented KKT system (pk_minres.cpp: pk_minres_begin_dev, pk_solve_kkt ...; free_minres, minres_forget)
-// Allocated on first use; every array grows when needed and never shrinks short of pk_set_problem.
-struct PkMinres {
-  double* d_work = nullptr;         // [r1 | r2 | y | v | w | w2 | q], n + m doubles each
-  size_t work_cap = 0;
-  double* d_partial = nullptr;      // the pieces' partial sums, 2 planes of n_pieces doubles
-  size_t partial_cap = 0;
-  double* d_rec = nullptr;          // the record of 16 doubles
-  size_t rec_cap = 0;
-  double* d_scratch = nullptr;      // the host forms' [b | x0 | x | s1 s2 | minv | v], n + m doubles each
-  size_t scratch_cap = 0;
-  // the solve in progress (pk_minres_begin_dev): the caller's arrays; forgotten by pk_set_csr_operator and pk_set_csr_map
-  bool active = false;
+// ---- CG on the condensed KKT matrix / the normal equations (pk_cg.cpp: pk_cg_begin_dev, pk_solve_condensed ...)
+// work [r | z | p | q | t] and scratch [b | x0 | x | d | s | minv | v] of max(n, m) doubles each, 3 planes, a record of 8 doubles
+struct PkCg : PkSolveState {
+  int form = 0;                     // the solve in progress: the caller's arrays
+  const double *jvals = nullptr, *hvals = nullptr, *d = nullptr, *s = nullptr, *minv = nullptr;
+  double* x = nullptr;
+};
+
+// ---- MINRES on the augmented KKT system (pk_minres.cpp: pk_minres_begin_dev, pk_solve_kkt ...)
+// work [r1 | r2 | y | v | w | w2 | q] and scratch [b | x0 | x | s1 s2 | minv | v] of n + m doubles each, 2 planes, a record of 16
+struct PkMinres : PkSolveState {
   const double *jvals = nullptr, *hvals = nullptr, *s1 = nullptr, *s2 = nullptr, *minv = nullptr;
   double* x = nullptr;
-  hipStream_t stream = nullptr;     // where the last begin / advance was enqueued: pk_minres_record copies behind it
 };
 
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
@@ -446,17 +442,60 @@ int op_linearized(pk_ctx* c, int op, const double*& vals, const char* who);
 // ---- pk_merit.cpp
 void free_merit(pk_ctx* c);          // bounds, partial rows and scratch (with the problem)
 
-// ---- pk_cg.cpp
-void free_cg(pk_ctx* c);             // work vectors, partial sums, record and scratch (with the problem)
-void cg_forget(pk_ctx* c);           // a solve in progress is forgotten: the operators or a map are about to change
-// An array of the context that grows when needed and never shrinks: the new one first, so error 136 enqueues nothing and leaves
-// what was there.  And the upload of an optional host array on the context's stream.  (Shared with pk_minres.cpp.)
-int cg_reserve(pk_ctx* c, double*& p, size_t& cap, size_t want, const char* who, const char* what);
-int cg_up(pk_ctx* c, double* dst, const double* src, size_t count);
+// ---- pk_solve.cpp: the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp (no kernels)
+// An array of the context that grows when needed and never shrinks: the new one first, so the error (code: 127 for the merit
+// terms, 136 for the solves) enqueues nothing and leaves what was there.  And the upload of an optional host array (src NULL:
+// nothing) on the context's stream.
+int lib_reserve(pk_ctx* c, double*& p, size_t& cap, size_t want, int code, const char* who, const char* what);
+int lib_upload(pk_ctx* c, double* dst, const double* src, size_t count);
+int solve_state(pk_ctx* c, PkSolveState& s, size_t work, size_t rec, const char* who);           // work vectors and record, on first use
+int solve_partial(pk_ctx* c, PkSolveState& s, int planes, int64_t len, const char* who);         // partial sums of `planes` dots of len
+inline bool solve_tol_ok(double tol) { return tol >= 0.0 && __builtin_isfinite(tol); }
+// what every entry point that applies K checks before anything is enqueued: no sharded context (119); J, J^T [, H] ready
+int solve_ops_ready(pk_ctx* c, bool with_h, bool pointers, const char* who);
+// the values pk_linearize left, for the host forms (118)
+int solve_linearized(pk_ctx* c, bool with_h, const double*& jvals, const double*& hvals, const char* who);
+// a host form's checks behind that, in this order: its parameters (134), the values pk_linearize left (118), the positions of
+// H's diagonal for the preconditioner built on the device (132)
+int solve_host_checks(pk_ctx* c, bool with_h, double tol, int maxiter, int check_every, int precond, const double*& jvals,
+                      const double*& hvals, const char* who);
+// The skeletons of the entry points behind ready(c) (theirs: the state is a member of the context it vouches for).  who names
+// the entry point in the messages, begin the one that starts a solve.  record: 60, 135, the copy behind the solve's stream,
+// synchronised.  advance: 134, 135, the stream, `iters` times the method's iteration.
+int solve_record(pk_ctx* c, const PkSolveState& s, double* rec, size_t count, const char* who, const char* begin);
+int solve_advance(pk_ctx* c, PkSolveState& s, int iters, void* stream, int (*iteration)(pk_ctx*, hipStream_t), const char* who,
+                  const char* begin);
+// The tail of a host form behind its begin: the record, then chunks of check_every iterations and the record again until the
+// status (slot 0) leaves 0 or maxiter is reached -- status 4 then, in the host copy only -- and the download of x.
+int solve_host_loop(pk_ctx* c, int maxiter, int check_every, int (*advance)(pk_ctx*, int, void*), int (*record)(pk_ctx*, double*),
+                    double* rec, double* x, const double* d_x, size_t count);
 
-// ---- pk_minres.cpp
-void free_minres(pk_ctx* c);         // work vectors, partial sums, record and scratch (with the problem)
-void minres_forget(pk_ctx* c);       // a solve in progress is forgotten: the operators or a map are about to change
+// an array cut into the slices [0, L), [L, 2 L) ...: one per double* member of Slices, in their order
+template <class Slices, size_t... K>
+inline Slices lib_slices_of(double* w, size_t L, std::index_sequence<K...>) { return Slices{(w + K * L)...}; }
+template <class Slices>
+inline Slices lib_slices(double* w, size_t L) { return lib_slices_of<Slices>(w, L, std::make_index_sequence<sizeof(Slices) / sizeof(double*)>{}); }
+// the host forms' scratch: one slice of L doubles per member of Slices
+template <class Slices>
+inline int solve_scratch(pk_ctx* c, PkSolveState& s, size_t L, Slices& out, const char* who) {
+  if (const int rc = lib_reserve(c, s.d_scratch, s.scratch_cap, sizeof(Slices) / sizeof(double*) * L, 136, who, "host-form scratch")) return rc;
+  out = lib_slices<Slices>(s.d_scratch, L);
+  return 0;
+}
+// with the problem: the arrays go, the state is a fresh one
+template <class Solver>
+inline void solve_free(Solver& s) {
+  release(s.d_work); release(s.d_partial); release(s.d_rec); release(s.d_scratch);
+  s = Solver{};
+}
+// the operators or a map are about to change: a solve in progress and the caller's pointers it holds are forgotten, the arrays stay
+template <class Solver>
+inline void solve_forget(Solver& s) {
+  PkSolveState arrays = s;
+  arrays.active = false;
+  s = Solver{};
+  static_cast<PkSolveState&>(s) = arrays;
+}
 
 // ---- the host-buffer form of an entry point: upload x (and lambda), the device-pointer entry point, download, synchronize
 inline int host_ready(pk_ctx* c, bool buffers) {

@@ -6,50 +6,11 @@
 // tear-down without a live allocation.  With --dump FILE: the solve FILE describes (tests/test_cg_cpu.py writes it from
 // tests/cg_cases.py) through begin / advance / record, x and the record printed as hex doubles.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <vector>
 
 #include "driver_common.h"
 
-typedef std::vector<double> Vec;
-static const int PAD = 5;
 enum { INIT = 0, CURVATURE = 1, UPDATE = 2, DIRECTION = 3, SCALE = 4, JACOBI = 5 };
-
-struct Guarded {
-  Vec buf;
-  size_t count;
-  explicit Guarded(size_t n, double fill = -77.0) : buf(n + 2 * PAD, fill), count(n) {
-    for (int i = 0; i < PAD; ++i) buf[(size_t)i] = buf[n + PAD + (size_t)i] = SENTINEL;
-  }
-  explicit Guarded(const Vec& v) : Guarded(v.size()) { std::copy(v.begin(), v.end(), buf.begin() + PAD); }
-  double* ptr() { return buf.data() + PAD; }
-  Vec fetch() const {
-    for (int i = 0; i < PAD; ++i) CHECK(buf[(size_t)i] == SENTINEL && buf[count + PAD + (size_t)i] == SENTINEL);
-    return Vec(buf.begin() + PAD, buf.begin() + PAD + (long)count);
-  }
-};
-
-// n doubles whose data() is never NULL (a length of 0 is a valid step; a null pointer is refused)
-static Vec made(size_t n) {
-  Vec v;
-  v.reserve(n + 1);
-  v.resize(n);
-  return v;
-}
-
-static Vec ints(size_t n, int64_t salt, bool positive = false) {
-  Vec v = made(n);
-  for (size_t i = 0; i < n; ++i) v[i] = positive ? (double)(((int64_t)i * 7 + salt) % 4 + 1) : small_vec((int64_t)i * 3 + salt);
-  return v;
-}
-
-static double dotp(const Vec& a, const Vec& b) {
-  double s = 0.0;
-  for (size_t i = 0; i < a.size(); ++i) s += a[i] * b[i];
-  return s;
-}
 
 static int step(int which, int64_t len, const double* b, const double* x0, const double* minv, const double* s, double* x, double* r,
                 double* z, double* p, double* q, double* rec, double tol) {
@@ -148,38 +109,12 @@ static void check_steps(size_t L) {
   }
 }
 
-// L + L^T - diag(L) of a lower-triangular L, each off-diagonal entry twice with one src (CsrMap.symmetric)
-static Csr symmetric(const Csr& L) {
-  struct E { int32_t c, s; };
-  std::vector<std::vector<E>> mirrored((size_t)L.rows);
-  for (int32_t r = 0; r < L.rows; ++r)
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e)
-      if (L.indices[(size_t)e] < r) mirrored[(size_t)L.indices[(size_t)e]].push_back({r, e});
-  Csr S;
-  S.rows = S.cols = L.rows;
-  S.indptr.push_back(0);
-  for (int32_t r = 0; r < L.rows; ++r) {
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e) { S.indices.push_back(L.indices[(size_t)e]); S.src.push_back(e); }
-    for (const E& m : mirrored[(size_t)r]) { S.indices.push_back(m.c); S.src.push_back(m.s); }
-    S.indptr.push_back((int32_t)S.indices.size());
-  }
-  return S;
-}
-
-static Vec matvec(const Csr& A, const Vec& vals, const Vec& v) {
-  Vec y((size_t)A.rows, 0.0);
-  for (int32_t r = 0; r < A.rows; ++r)
-    for (int32_t e = A.indptr[(size_t)r]; e < A.indptr[(size_t)r + 1]; ++e)
-      y[(size_t)r] += vals[(size_t)(A.src.empty() ? e : A.src[(size_t)e])] * v[(size_t)A.indices[(size_t)e]];
-  return y;
-}
-
 // K v by plain loops; d, s, hvals may be NULL
 static Vec reference_kv(int form, const Csr& A, const Csr& T, const Csr& S, const Vec& jv, const Vec* hv, const Vec* d, const Vec* s, const Vec& v) {
-  Vec t = matvec(form == 0 ? A : T, jv, v);
+  Vec t = matvec(form == 0 ? A : T, jv, v.data());
   if (d) for (size_t i = 0; i < t.size(); ++i) t[i] = (*d)[i] * t[i];
-  Vec y = matvec(form == 0 ? T : A, jv, t);
-  if (hv) { const Vec h = matvec(S, *hv, v); for (size_t i = 0; i < y.size(); ++i) y[i] += h[i]; }
+  Vec y = matvec(form == 0 ? T : A, jv, t.data());
+  if (hv) { const Vec h = matvec(S, *hv, v.data()); for (size_t i = 0; i < y.size(); ++i) y[i] += h[i]; }
   if (s) for (size_t i = 0; i < y.size(); ++i) y[i] += (*s)[i] * v[i];
   return y;
 }
@@ -195,38 +130,7 @@ static void device_solve(int form, const double* jv, const double* hv, const dou
   }
 }
 
-static bool same_bits(const Vec& a, const Vec& b) { return a.size() == b.size() && std::memcmp(a.data(), b.data(), 8 * a.size()) == 0; }
-
-static void load_model() {
-  OK(pk_create(&ctx, 0));
-  pk_model_desc md{};
-  md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
-  md.ne_j = md.ne_h = md.ne_a = 1; md.tab_cap = 64;
-  OK(pk_load_model(ctx, image, sizeof image, &md));
-}
-
 // ---------------------------------------------------------------- --dump: the solve a file describes
-static std::vector<int32_t> read_ints(FILE* f) {
-  size_t n = 0;
-  if (std::fscanf(f, "%zu", &n) != 1) std::exit(3);
-  std::vector<int32_t> v(n);
-  for (auto& e : v) if (std::fscanf(f, "%d", &e) != 1) std::exit(3);
-  return v;
-}
-static Vec read_doubles(FILE* f) {
-  size_t n = 0;
-  if (std::fscanf(f, "%zu", &n) != 1) std::exit(3);
-  Vec v(n);
-  for (auto& e : v) if (std::fscanf(f, "%la", &e) != 1) std::exit(3);
-  return v;
-}
-static Csr read_csr(FILE* f, int32_t cols) {
-  Csr A;
-  A.indptr = read_ints(f); A.indices = read_ints(f); A.src = read_ints(f);
-  A.rows = (int32_t)A.indptr.size() - 1; A.cols = cols;
-  return A;
-}
-
 static int dump(const char* path) {
   FILE* f = std::fopen(path, "r");
   if (!f) return 3;

@@ -1,12 +1,15 @@
 // driver_common.h -- TEST INFRASTRUCTURE: what the driver programs of this directory share (header-only; every driver is a
 // program of its own, so everything here is inline).  The counted checks, the context, the smallest problem the runtime
-// accepts, and -- for the two operator drivers -- synthetic CSR structures of small integers.
+// accepts, synthetic CSR structures of small integers for the drivers of the operators, and for the drivers of the units built on
+// them (reductions, CG, MINRES): results between sentinels, vectors of small integers, plain-loop products, the reader of --dump.
 #ifndef FAKE_HIP_DRIVER_COMMON_H
 #define FAKE_HIP_DRIVER_COMMON_H
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../../include/pockit_hip.h"
@@ -107,5 +110,106 @@ inline int set_operator(int op, const Csr& A) {
 
 inline double small_val(int64_t e) { return (double)((e * 31) % 17 - 8); }
 inline double small_vec(int64_t j) { return (double)((j * 13) % 11 - 5); }
+
+// ---------------------------------------------------------------- vectors between sentinels, small integers, exact comparisons
+typedef std::vector<double> Vec;
+inline const int PAD = 5;
+
+// a result between sentinels: what was written, nothing beside it
+struct Guarded {
+  Vec buf;
+  size_t count;
+  explicit Guarded(size_t n, double fill = -77.0) : buf(n + 2 * PAD, fill), count(n) {
+    for (int i = 0; i < PAD; ++i) buf[(size_t)i] = buf[n + PAD + (size_t)i] = SENTINEL;
+  }
+  explicit Guarded(const Vec& v) : Guarded(v.size()) { std::copy(v.begin(), v.end(), buf.begin() + PAD); }
+  double* ptr() { return buf.data() + PAD; }
+  Vec fetch() const {
+    for (int i = 0; i < PAD; ++i) CHECK(buf[(size_t)i] == SENTINEL && buf[count + PAD + (size_t)i] == SENTINEL);
+    return Vec(buf.begin() + PAD, buf.begin() + PAD + (long)count);
+  }
+};
+
+// n doubles whose data() is never NULL (a length of 0 is a valid step; a null pointer is refused)
+inline Vec made(size_t n) {
+  Vec v;
+  v.reserve(n + 1);
+  v.resize(n);
+  return v;
+}
+
+inline Vec ints(size_t n, int64_t salt, bool positive = false) {
+  Vec v = made(n);
+  for (size_t i = 0; i < n; ++i) v[i] = positive ? (double)(((int64_t)i * 7 + salt) % 4 + 1) : small_vec((int64_t)i * 3 + salt);
+  return v;
+}
+
+inline double dotp(const Vec& a, const Vec& b) {
+  double s = 0.0;
+  for (size_t i = 0; i < a.size(); ++i) s += a[i] * b[i];
+  return s;
+}
+
+inline bool same_bits(const Vec& a, const Vec& b) { return a.size() == b.size() && std::memcmp(a.data(), b.data(), 8 * a.size()) == 0; }
+
+// L + L^T - diag(L) of a lower-triangular L, each off-diagonal entry twice with one src (CsrMap.symmetric)
+inline Csr symmetric(const Csr& L) {
+  struct E { int32_t c, s; };
+  std::vector<std::vector<E>> mirrored((size_t)L.rows);
+  for (int32_t r = 0; r < L.rows; ++r)
+    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e) {
+      const int32_t c = L.indices[(size_t)e];
+      if (c > r) std::exit(2);
+      if (c < r) mirrored[(size_t)c].push_back({r, e});      // rows ascend, so the mirrored entries of a row arrive in column order
+    }
+  Csr S;
+  S.rows = S.cols = L.rows;
+  S.indptr.push_back(0);
+  for (int32_t r = 0; r < L.rows; ++r) {
+    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e) { S.indices.push_back(L.indices[(size_t)e]); S.src.push_back(e); }
+    for (const E& m : mirrored[(size_t)r]) { S.indices.push_back(m.c); S.src.push_back(m.s); }
+    S.indptr.push_back((int32_t)S.indices.size());
+  }
+  return S;
+}
+
+inline Vec matvec(const Csr& A, const Vec& vals, const double* v) {
+  Vec y((size_t)A.rows, 0.0);
+  for (int32_t r = 0; r < A.rows; ++r)
+    for (int32_t e = A.indptr[(size_t)r]; e < A.indptr[(size_t)r + 1]; ++e)
+      y[(size_t)r] += vals[(size_t)(A.src.empty() ? e : A.src[(size_t)e])] * v[(size_t)A.indices[(size_t)e]];
+  return y;
+}
+
+// the context with the smallest model the runtime accepts
+inline void load_model() {
+  OK(pk_create(&ctx, 0));
+  pk_model_desc md{};
+  md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
+  md.ne_j = md.ne_h = md.ne_a = 1; md.tab_cap = 64;
+  OK(pk_load_model(ctx, image, sizeof image, &md));
+}
+
+// ---------------------------------------------------------------- --dump: reading the solve a file describes
+inline std::vector<int32_t> read_ints(FILE* f) {
+  size_t n = 0;
+  if (std::fscanf(f, "%zu", &n) != 1) std::exit(3);
+  std::vector<int32_t> v(n);
+  for (auto& e : v) if (std::fscanf(f, "%d", &e) != 1) std::exit(3);
+  return v;
+}
+inline Vec read_doubles(FILE* f) {
+  size_t n = 0;
+  if (std::fscanf(f, "%zu", &n) != 1) std::exit(3);
+  Vec v(n);
+  for (auto& e : v) if (std::fscanf(f, "%la", &e) != 1) std::exit(3);
+  return v;
+}
+inline Csr read_csr(FILE* f, int32_t cols) {
+  Csr A;
+  A.indptr = read_ints(f); A.indices = read_ints(f); A.src = read_ints(f);
+  A.rows = (int32_t)A.indptr.size() - 1; A.cols = cols;
+  return A;
+}
 
 #endif  // FAKE_HIP_DRIVER_COMMON_H

@@ -103,11 +103,7 @@ static void reduce_case(int B, int64_t n_g, int64_t n_x, bool with_d, bool poiso
 }
 
 int main() {
-  OK(pk_create(&ctx, 0));
-  pk_model_desc md{};
-  md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
-  md.ne_j = md.ne_h = md.ne_a = 1; md.tab_cap = 64;
-  OK(pk_load_model(ctx, image, sizeof image, &md));
+  load_model();
   const int32_t n = 40, m = 30;
   const int64_t nnz_J = 200;
   {

@@ -8,54 +8,13 @@
 // writes it from tests/minres_cases.py) through begin / advance / record, the record and x printed as hex doubles.
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <set>
-#include <vector>
 
 #include "driver_common.h"
 
-typedef std::vector<double> Vec;
-static const int PAD = 5;
 enum { INIT = 0, LANCZOS = 1, ALFA = 2, UPDATE = 3, SOLUTION = 4, DIAG = 5, RECIP = 6 };
 enum { STATUS = 0, ITERS, PHIBAR, THR, BETA, OLDB, ALFA_, DBAR, EPSLN, CS, SN, PHI, OLDEPS, DELTA, GAMMA, FRESH };
-
-struct Guarded {
-  Vec buf;
-  size_t count;
-  explicit Guarded(size_t n, double fill = -77.0) : buf(n + 2 * PAD, fill), count(n) {
-    for (int i = 0; i < PAD; ++i) buf[(size_t)i] = buf[n + PAD + (size_t)i] = SENTINEL;
-  }
-  explicit Guarded(const Vec& v) : Guarded(v.size()) { std::copy(v.begin(), v.end(), buf.begin() + PAD); }
-  double* ptr() { return buf.data() + PAD; }
-  Vec fetch() const {
-    for (int i = 0; i < PAD; ++i) CHECK(buf[(size_t)i] == SENTINEL && buf[count + PAD + (size_t)i] == SENTINEL);
-    return Vec(buf.begin() + PAD, buf.begin() + PAD + (long)count);
-  }
-};
-
-// n doubles whose data() is never NULL (a length of 0 is a valid step; a null pointer is refused)
-static Vec made(size_t n) {
-  Vec v;
-  v.reserve(n + 1);
-  v.resize(n);
-  return v;
-}
-
-static Vec ints(size_t n, int64_t salt, bool positive = false) {
-  Vec v = made(n);
-  for (size_t i = 0; i < n; ++i) v[i] = positive ? (double)(((int64_t)i * 7 + salt) % 4 + 1) : small_vec((int64_t)i * 3 + salt);
-  return v;
-}
-
-static double dotp(const Vec& a, const Vec& b) {
-  double s = 0.0;
-  for (size_t i = 0; i < a.size(); ++i) s += a[i] * b[i];
-  return s;
-}
-
-static bool same_bits(const Vec& a, const Vec& b) { return a.size() == b.size() && std::memcmp(a.data(), b.data(), 8 * a.size()) == 0; }
 
 struct StepArgs {
   const double *b = nullptr, *x0 = nullptr, *minv = nullptr, *s1 = nullptr, *s2 = nullptr;
@@ -249,32 +208,6 @@ static void check_steps(size_t L) {
   }
 }
 
-// L + L^T - diag(L) of a lower-triangular L, each off-diagonal entry twice with one src (CsrMap.symmetric)
-static Csr symmetric(const Csr& L) {
-  struct E { int32_t c, s; };
-  std::vector<std::vector<E>> mirrored((size_t)L.rows);
-  for (int32_t r = 0; r < L.rows; ++r)
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e)
-      if (L.indices[(size_t)e] < r) mirrored[(size_t)L.indices[(size_t)e]].push_back({r, e});
-  Csr S;
-  S.rows = S.cols = L.rows;
-  S.indptr.push_back(0);
-  for (int32_t r = 0; r < L.rows; ++r) {
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e) { S.indices.push_back(L.indices[(size_t)e]); S.src.push_back(e); }
-    for (const E& m : mirrored[(size_t)r]) { S.indices.push_back(m.c); S.src.push_back(m.s); }
-    S.indptr.push_back((int32_t)S.indices.size());
-  }
-  return S;
-}
-
-static Vec matvec(const Csr& A, const Vec& vals, const double* v) {
-  Vec y((size_t)A.rows, 0.0);
-  for (int32_t r = 0; r < A.rows; ++r)
-    for (int32_t e = A.indptr[(size_t)r]; e < A.indptr[(size_t)r + 1]; ++e)
-      y[(size_t)r] += vals[(size_t)(A.src.empty() ? e : A.src[(size_t)e])] * v[(size_t)A.indices[(size_t)e]];
-  return y;
-}
-
 // K v by plain loops; s1, s2, hvals may be NULL
 static Vec reference_kv(const Csr& A, const Csr& T, const Csr& S, const Vec& jv, const Vec* hv, const Vec* s1, const Vec* s2, const Vec& v) {
   const size_t n = (size_t)A.cols, m = (size_t)A.rows;
@@ -295,36 +228,6 @@ static void device_solve(const double* jv, const double* hv, const double* s1, c
     OK(pk_minres_advance_dev(ctx, std::min(chunk, maxiter - done), nullptr));
     OK(pk_minres_record(ctx, rec));
   }
-}
-
-static void load_model() {
-  OK(pk_create(&ctx, 0));
-  pk_model_desc md{};
-  md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
-  md.ne_j = md.ne_h = md.ne_a = 1; md.tab_cap = 64;
-  OK(pk_load_model(ctx, image, sizeof image, &md));
-}
-
-// ---------------------------------------------------------------- --dump: the solve a file describes
-static std::vector<int32_t> read_ints(FILE* f) {
-  size_t n = 0;
-  if (std::fscanf(f, "%zu", &n) != 1) std::exit(3);
-  std::vector<int32_t> v(n);
-  for (auto& e : v) if (std::fscanf(f, "%d", &e) != 1) std::exit(3);
-  return v;
-}
-static Vec read_doubles(FILE* f) {
-  size_t n = 0;
-  if (std::fscanf(f, "%zu", &n) != 1) std::exit(3);
-  Vec v(n);
-  for (auto& e : v) if (std::fscanf(f, "%la", &e) != 1) std::exit(3);
-  return v;
-}
-static Csr read_csr(FILE* f, int32_t cols) {
-  Csr A;
-  A.indptr = read_ints(f); A.indices = read_ints(f); A.src = read_ints(f);
-  A.rows = (int32_t)A.indptr.size() - 1; A.cols = cols;
-  return A;
 }
 
 static int dump(const char* path) {

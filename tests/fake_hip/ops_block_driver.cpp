@@ -127,11 +127,7 @@ static void jacobian_case(const std::vector<int32_t>& lens, int32_t cols) {
 }
 
 int main() {
-  OK(pk_create(&ctx, 0));
-  pk_model_desc md{};
-  md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
-  md.ne_j = md.ne_h = md.ne_a = 1; md.tab_cap = 64;
-  OK(pk_load_model(ctx, image, sizeof image, &md));
+  load_model();
 
   // ---- the row lengths at which the walk changes, mixed; 600 consecutive empty rows; a long row first and last, and alone
   jacobian_case({0, 1, 255, 256, 257, 512, 513, 0, 3, 1, 0}, 600);

@@ -11,28 +11,6 @@
 #include "driver_common.h"
 #include "../../pockit_amd/csrc/pk_runtime.h"      // (pk_op_row_blocks and the context's operator tables)
 
-// L + L^T - diag(L) of a lower-triangular L, each off-diagonal entry twice with one src (CsrMap.symmetric)
-static Csr symmetric(const Csr& L) {
-  struct E { int32_t r, c, s; };
-  std::vector<std::vector<E>> by_row((size_t)L.rows);
-  for (int32_t r = 0; r < L.rows; ++r)
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e) {
-      const int32_t c = L.indices[(size_t)e];
-      if (c > r) std::exit(2);
-      if (c < r) by_row[(size_t)c].push_back({c, r, e});      // rows ascend, so the mirrored entries of a row arrive in column order
-    }
-  Csr S;
-  S.rows = S.cols = L.rows;
-  S.indptr.push_back(0);
-  for (int32_t r = 0; r < L.rows; ++r) {
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e) { S.indices.push_back(L.indices[(size_t)e]); S.src.push_back(e); }
-    for (const E& m : by_row[(size_t)r]) { S.indices.push_back(m.c); S.src.push_back(m.s); }
-    S.indptr.push_back((int32_t)S.indices.size());
-  }
-  return S;
-}
-
-
 // the reference: a plain loop over rows, entries and the optional addend
 static std::vector<double> reference(const Csr& A, const std::vector<double>& vals, const std::vector<double>& v, const double* add) {
   std::vector<double> y((size_t)A.rows);
@@ -112,11 +90,7 @@ static void jacobian_case(const std::vector<int32_t>& lens, int32_t cols) {
 }
 
 int main() {
-  OK(pk_create(&ctx, 0));
-  pk_model_desc md{};
-  md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
-  md.ne_j = md.ne_h = md.ne_a = 1; md.tab_cap = 64;
-  OK(pk_load_model(ctx, image, sizeof image, &md));
+  load_model();
 
   // ---- the row lengths at which the walk changes, mixed; 600 consecutive empty rows; a long row first and last
   jacobian_case({0, 1, 255, 256, 257, 512, 513, 0, 3, 1, 0}, 600);

@@ -10,8 +10,6 @@
 
 #include "driver_common.h"
 
-static const int PAD = 5;
-
 // the reference: a plain loop over rows and entries; w and add may be NULL
 static std::vector<double> reference(const Csr& A, int mode, const std::vector<double>& vals, const double* w, const double* add) {
   std::vector<double> y((size_t)A.rows);
@@ -28,20 +26,6 @@ static std::vector<double> reference(const Csr& A, int mode, const std::vector<d
   }
   return y;
 }
-
-// y between sentinels: the rows written, nothing beside them
-struct Guarded {
-  std::vector<double> buf;
-  size_t count;
-  explicit Guarded(size_t n, double fill = -77.0) : buf(n + 2 * PAD, fill), count(n) {
-    for (int i = 0; i < PAD; ++i) buf[(size_t)i] = buf[n + PAD + (size_t)i] = SENTINEL;
-  }
-  double* ptr() { return buf.data() + PAD; }
-  std::vector<double> fetch() const {
-    for (int i = 0; i < PAD; ++i) CHECK(buf[(size_t)i] == SENTINEL && buf[count + PAD + (size_t)i] == SENTINEL);
-    return std::vector<double>(buf.begin() + PAD, buf.begin() + PAD + (long)count);
-  }
-};
 
 static void check_nonnegative(const std::vector<double>& y) {
   for (double v : y) CHECK(v >= 0.0 && !std::signbit(v));
@@ -81,24 +65,6 @@ static void jacobian_case(const std::vector<int32_t>& lens, int32_t cols) {
   check_reductions(1, T, vals);
 }
 
-// L + L^T - diag(L) of a lower-triangular L, each off-diagonal entry twice with one src (CsrMap.symmetric)
-static Csr symmetric(const Csr& L) {
-  struct E { int32_t c, s; };
-  std::vector<std::vector<E>> mirrored((size_t)L.rows);
-  for (int32_t r = 0; r < L.rows; ++r)
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e)
-      if (L.indices[(size_t)e] < r) mirrored[(size_t)L.indices[(size_t)e]].push_back({r, e});
-  Csr S;
-  S.rows = S.cols = L.rows;
-  S.indptr.push_back(0);
-  for (int32_t r = 0; r < L.rows; ++r) {
-    for (int32_t e = L.indptr[(size_t)r]; e < L.indptr[(size_t)r + 1]; ++e) { S.indices.push_back(L.indices[(size_t)e]); S.src.push_back(e); }
-    for (const E& m : mirrored[(size_t)r]) { S.indices.push_back(m.c); S.src.push_back(m.s); }
-    S.indptr.push_back((int32_t)S.indices.size());
-  }
-  return S;
-}
-
 // CsrMap.diagonal_src: the last entry of a row whose column equals the row, -1 where there is none
 static std::vector<int32_t> diagonal_src(const Csr& L) {
   std::vector<int32_t> pos((size_t)L.rows, -1);
@@ -116,11 +82,7 @@ static std::vector<double> diagonal(const std::vector<int32_t>& pos, const std::
 }
 
 int main() {
-  OK(pk_create(&ctx, 0));
-  pk_model_desc md{};
-  md.n_phase = 1; md.n_I = 1; md.nred = 1; md.lds_g = md.lds_j = md.lds_h = md.lds_x = md.lds_e = md.lds_jc = 64;
-  md.ne_j = md.ne_h = md.ne_a = 1; md.tab_cap = 64;
-  OK(pk_load_model(ctx, image, sizeof image, &md));
+  load_model();
 
   // ---- the row lengths at which the walk changes, mixed; 600 consecutive empty rows; a long row first and last
   jacobian_case({0, 1, 255, 256, 257, 512, 513, 0, 3, 1, 0}, 600);

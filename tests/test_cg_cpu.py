@@ -2,8 +2,8 @@
 host-only stand-in of the HIP runtime and driven by tests/fake_hip/cg_driver.cpp: the stand-in walk of every vector step against
 plain loops, K in both forms, the refusals, the host form against begin / advance / record, what frees and forgets the state; with
 ``--dump`` one synthetic solve compared BIT FOR BIT with the emulator of tests/cg_cases.py, so the documented association is held
-on the CPU as well; and the new unit leaves what the runtime enqueues elsewhere as tests/fake_hip/launch_trace.txt recorded it.
-CPU only; a stand-alone program (its own main): nothing sanitized is loaded into Python."""
+on the CPU as well.  (That the unit leaves what the runtime enqueues elsewhere as tests/fake_hip/launch_trace.txt recorded it is
+tests/test_runtime_sanitized.py's test of the launch shapes.)  CPU only; a stand-alone program (its own main): nothing sanitized is loaded into Python."""
 import os
 import shutil
 import subprocess
@@ -13,7 +13,7 @@ import pytest
 
 import cg_cases as cg
 import sparse_cases as sc
-from sanitized_build import FAKE, sanitized_driver
+from sanitized_build import sanitized_driver
 
 ENV = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
@@ -73,12 +73,3 @@ def test_the_host_walk_matches_the_emulator_bit_for_bit(driver, tmp_path, ctx, f
     assert want_rec[cg.STATUS] == (1.0 if pd else 2.0)
     assert sc.same_bits(rec, want_rec), (rec, want_rec)
     assert sc.same_bits(x, want_x)
-
-
-def test_the_recorded_launch_trace_is_unchanged_with_the_new_unit_in_the_library(tmp_path):
-    with open(os.path.join(FAKE, "launch_trace.txt")) as fh:
-        recorded = fh.read().split("\n", 1)[1]
-    exe = sanitized_driver("driver.cpp", tmp_path)
-    run = subprocess.run([exe, "--launch-trace"], capture_output=True, text=True, env=dict(os.environ, **ENV), timeout=600)
-    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-6000:])
-    assert run.stdout == recorded

@@ -14,78 +14,25 @@ Models (the cases of tests/test_gpu_csr_operators.py) against SciPy on the ORACL
 form, H, d and shift at that file's rule scaled by the three products composed; the solves with the inputs and the bounds the
 module constants state: status 1, ``|b - K x| <= 2 tol |b|`` and ``max|x - spsolve| <= 2 tol |b| / lambda``
 (``e = K^-1 r``; the factor 2 covers the 1e-11 parity of the matrices times cond(K) < 1e2, three orders below tol)."""
-import importlib
-
 import numpy as np
 import pytest
 import scipy.sparse
 import scipy.sparse.linalg
 
 import cg_cases as cg
-import models
 import sparse_cases as sc
+from device_cases import Buf, SyntheticContext, _ptr, _same, _up, step_ev  # noqa: F401  (step_ev: a fixture)
 from test_gpu_csr_operators import CASES, Case
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error::RuntimeWarning")]
 
-PAD, SENTINEL = 8, -7.25e77
 TOL, MAXITER = 1e-8, 64
 INIT, CURVATURE, UPDATE, DIRECTION, SCALE, JACOBI = range(6)
-
-
-def _i32(a):
-    from pockit_amd import runtime
-
-    return np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(runtime.c_int32_p)
-
-
-class Buf:
-    """``count`` doubles in the middle of a larger device tensor, between sentinels: NaN, or ``content``."""
-
-    def __init__(self, count, content=None):
-        import torch
-
-        host = np.full(count + 2 * PAD, np.nan)
-        host[:PAD] = host[PAD + count:] = SENTINEL
-        if content is not None:
-            host[PAD: PAD + count] = content
-        self.count, self.t = count, torch.from_numpy(host).to(torch.device("cuda", 0))
-        self.ptr = self.t.data_ptr() + 8 * PAD
-
-    def fetch(self):
-        host = self.t.cpu().numpy()
-        edge = np.full(PAD, SENTINEL)
-        assert sc.same_bits(host[:PAD], edge) and sc.same_bits(host[PAD + self.count:], edge), "a sentinel was overwritten"
-        return host[PAD: PAD + self.count].copy()
-
-
-def _up(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(torch.device("cuda", 0))
-
-
-def _ptr(t):
-    return None if t is None else t.ptr if isinstance(t, Buf) else t.data_ptr()
-
-
-@pytest.fixture(scope="module")
-def step_ev():
-    import pockit_amd.radau as radau
-
-    ev = models.brachistochrone(radau, 3, 4)[0].evaluator
-    yield ev
-    ev.close()
 
 
 def _step(ev, step, length, b=None, x0=None, minv=None, s=None, x=None, r=None, z=None, p=None, q=None, rec=None, tol=0.0):
     ev.ctx.check(ev.ctx.lib.pk_cg_step_dev(ev.ctx.handle, step, length, _ptr(b), _ptr(x0), _ptr(minv), _ptr(s), _ptr(x), _ptr(r), _ptr(z),
                                            _ptr(p), _ptr(q), _ptr(rec), tol, None))
-
-
-def _same(what, got, want):
-    differ = np.flatnonzero(np.asarray(got).view(np.uint64) != np.asarray(want).view(np.uint64))
-    assert len(differ) == 0, f"{what}: {len(differ)} entries differ in bits from the emulator, first {differ[:6]}: {got[differ[:6]]} for {want[differ[:6]]}"
 
 
 def _check_steps(ev, L, full):
@@ -225,29 +172,7 @@ def test_step_refusals(step_ev):
 
 
 # ---------------------------------------------------------------- synthetic systems on contexts A and B
-class Synthetic:
-    """The evaluator of a context with the structures of cg_cases.System as its operators; ``real``: the same structures over
-    the values pk_linearize leaves (what the host form reads)."""
-
-    def __init__(self, ctx):
-        name, scheme, mesh, num_point = sc.CONTEXTS[ctx]["model"]
-        system, _, guess = getattr(models, name)(importlib.import_module(f"pockit_amd.{scheme}"), mesh, num_point)
-        self.ev = ev = system.evaluator
-        x, lam, sigma = models.bench_inputs(system, guess)
-        c = sc.CONTEXTS[ctx]
-        assert (ev.csr_map("jac").nnz, ev.csr_map("hess").nnz) == (c["nnz_j"], c["nnz_h"])
-        vals_j, vals_h = ev.jacobian_csr(x), ev.hessian_csr(x, lam, sigma)
-        self.random = cg.system(ctx)
-        self.real = cg.System(ctx, cg.SEEDS[ctx], values=(vals_j, vals_h))
-        lib, h = ev.ctx.lib, ev.ctx.handle
-        sy = self.random
-        for op, st in ((0, sy.J), (1, sy.JT), (2, sy.H)):
-            ev.ctx.check(lib.pk_set_csr_operator(h, op, _i32(st.indptr), _i32(st.indices), _i32(st.src), st.n_rows, st.n_cols, st.nnz))
-        ev.ctx.check(lib.pk_set_operator_diagonal(h, 2, _i32(sy.diag_pos), sy.n))
-        from pockit_amd import runtime
-
-        ev.ctx.check(lib.pk_linearize(h, runtime.as_dp(np.ascontiguousarray(x)), runtime.as_dp(np.ascontiguousarray(lam)), float(sigma)))
-
+class Synthetic(SyntheticContext):
     def device_solve(self, sy, inp, minv, x0, chunk):
         """begin / advance / record on device pointers: (x, rec)"""
         import torch

@@ -17,7 +17,6 @@ H, s1 and s2 at that file's rule scaled by the three products composed; the solv
 (quasi-definite: no eigenvalue in (-0.5, rho)) with status 1 within the reference count plus 10 %,
 ``|b - K x|_M <= 2 tol |b|_M`` and ``max|x - x*| <= 2 tol |b|_M / sqrt(min minv) / 0.5`` (``e = K^-1 r``,
 ``|r|_2 <= |r|_M / sqrt(min minv)``; the factor 2 is the one tests/test_minres_cases_cpu.py holds on the emulator)."""
-import importlib
 import math
 
 import numpy as np
@@ -27,78 +26,20 @@ import scipy.sparse.linalg
 
 import cg_cases as cg
 import minres_cases as mr
-import models
 import sparse_cases as sc
+from device_cases import Buf, SyntheticContext, _ptr, _same, _sync, _up, step_ev  # noqa: F401  (step_ev: a fixture)
 from test_gpu_csr_operators import CASES, Case
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error::RuntimeWarning")]
 
-PAD, SENTINEL = 8, -7.25e77
 TOL = 1e-8
 VECTORS = ("x", "r1", "r2", "y", "v", "w", "w2", "q")
-
-
-def _i32(a):
-    from pockit_amd import runtime
-
-    return np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(runtime.c_int32_p)
-
-
-class Buf:
-    """``count`` doubles in the middle of a larger device tensor, between sentinels: NaN, or ``content``."""
-
-    def __init__(self, count, content=None):
-        import torch
-
-        host = np.full(count + 2 * PAD, np.nan)
-        host[:PAD] = host[PAD + count:] = SENTINEL
-        if content is not None:
-            host[PAD: PAD + count] = content
-        self.count, self.t = count, torch.from_numpy(host).to(torch.device("cuda", 0))
-        self.ptr = self.t.data_ptr() + 8 * PAD
-
-    def fetch(self):
-        host = self.t.cpu().numpy()
-        edge = np.full(PAD, SENTINEL)
-        assert sc.same_bits(host[:PAD], edge) and sc.same_bits(host[PAD + self.count:], edge), "a sentinel was overwritten"
-        return host[PAD: PAD + self.count].copy()
-
-
-def _up(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(torch.device("cuda", 0))
-
-
-def _ptr(t):
-    return None if t is None else t.ptr if isinstance(t, Buf) else t.data_ptr()
-
-
-def _sync():
-    import torch
-
-    torch.cuda.synchronize()            # torch's copies run on its own stream; the context uses its own
-
-
-@pytest.fixture(scope="module")
-def step_ev():
-    import pockit_amd.radau as radau
-
-    ev = models.brachistochrone(radau, 3, 4)[0].evaluator
-    yield ev
-    ev.close()
 
 
 def _step(ev, step, length, split=0, b=None, x0=None, minv=None, s1=None, s2=None, x=None, r1=None, r2=None, y=None, v=None, w=None, w2=None,
           q=None, rec=None, tol=0.0):
     ev.ctx.check(ev.ctx.lib.pk_minres_step_dev(ev.ctx.handle, step, length, split, _ptr(b), _ptr(x0), _ptr(minv), _ptr(s1), _ptr(s2), _ptr(x),
                                                _ptr(r1), _ptr(r2), _ptr(y), _ptr(v), _ptr(w), _ptr(w2), _ptr(q), _ptr(rec), tol, None))
-
-
-def _same(what, got, want):
-    got, want = np.asarray(got), np.asarray(want)
-    differ = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
-    assert len(differ) == 0, f"{what}: {len(differ)} entries differ in bits from the emulator, first {differ[:6]}: {got[differ[:6]]} for {want[differ[:6]]}"
 
 
 def _running(length, iterations=3.0):
@@ -311,28 +252,12 @@ def test_step_refusals(step_ev):
 
 
 # ---------------------------------------------------------------- synthetic systems on contexts A and B
-class Synthetic:
-    """The evaluator of a context with the structures of cg_cases.System as its operators; ``real``: the same structures over
-    the values pk_linearize leaves (what the host form reads)."""
+class Synthetic(SyntheticContext):
+    """... and the KKT systems of minres_cases over the two systems."""
 
     def __init__(self, ctx):
-        from pockit_amd import runtime
-
-        name, scheme, mesh, num_point = sc.CONTEXTS[ctx]["model"]
-        system, _, guess = getattr(models, name)(importlib.import_module(f"pockit_amd.{scheme}"), mesh, num_point)
-        self.ev = ev = system.evaluator
-        x, lam, sigma = models.bench_inputs(system, guess)
-        c = sc.CONTEXTS[ctx]
-        assert (ev.csr_map("jac").nnz, ev.csr_map("hess").nnz) == (c["nnz_j"], c["nnz_h"])
-        vals_j, vals_h = ev.jacobian_csr(x), ev.hessian_csr(x, lam, sigma)
-        self.random = mr.kkt(ctx)
-        self.real = mr.Kkt(cg.System(ctx, cg.SEEDS[ctx], values=(vals_j, vals_h)))
-        lib, h = ev.ctx.lib, ev.ctx.handle
-        sy = self.random.sy
-        for op, st in ((0, sy.J), (1, sy.JT), (2, sy.H)):
-            ev.ctx.check(lib.pk_set_csr_operator(h, op, _i32(st.indptr), _i32(st.indices), _i32(st.src), st.n_rows, st.n_cols, st.nnz))
-        ev.ctx.check(lib.pk_set_operator_diagonal(h, 2, _i32(sy.diag_pos), sy.n))
-        ev.ctx.check(lib.pk_linearize(h, runtime.as_dp(np.ascontiguousarray(x)), runtime.as_dp(np.ascontiguousarray(lam)), float(sigma)))
+        super().__init__(ctx)
+        self.random, self.real = mr.Kkt(self.random), mr.Kkt(self.real)
 
     def device_solve(self, kk, inp, minv, x0, chunk, limit=400):
         """begin / advance / record on device pointers: (x, rec)"""
