@@ -422,6 +422,47 @@ int pk_solve_kkt(pk_ctx* ctx, int with_h, const double* s1, const double* s2, in
                  const double* b, const double* x0 /* or NULL */, double tol, int maxiter, int check_every, double* x,
                  double* rec /* 16 */);
 
+/* WHAT A PRIMAL-DUAL INTERIOR-POINT ITERATION NEEDS AROUND ITS SOLVE, where the vectors lie (kernels pk_ip_terms_k, pk_ip_resid_k,
+ * pk_ip_step_k, pk_ip_scalar_k of the library; pk_ipm.cpp).  A BOXED VECTOR is v of length L with the bounds
+ * of pk_set_bounds: which = 0 the n variables (v_lb, v_ub), which = 1 the m slacks of the constraint rows (c_lb, c_ub).  Per
+ * element lb == ub is fixed and has no side; otherwise a side is present when its bound is finite; dl = v - lb, du = ub - v.  An
+ * absent side contributes no term and nothing of it is read.  A present side is BAD when its slack is not > 0 or not finite or its
+ * multiplier is negative or not finite: counted, left out of every other column, 0.0 in its bracket.
+ * pk_ip_terms_dev: sigma_i = [zl_i / dl] + [zu_i / du] and rbar_i = [mu / dl] - [mu / du] (a single present bracket stored as it
+ * is, 0.0 without a side) and a record of 8: 0 compl_inf = max |dl zl - mu|, |du zu - mu|; 1 compl_sum = sum dl zl + sum du zu;
+ * 2 sides (good ones, counted); 3 min_slack (+inf without a side); 4 log_sum = sum ln dl + sum ln du; 5 bad; 6 z_sum; 7 min_compl
+ * = min dl zl, du zu (+inf without a side).
+ * pk_dual_residual_dev: t = J^T lambda + grad by pk_apply_operator_dev (op 1, add = grad; d_jvals the CSR values of the Jacobian
+ * map, as pk_kkt_apply_dev takes them), then r_i = t_i - z_i (d_z NULL: no term), negated when negate != 0, 0.0 for a fixed
+ * variable; a record of 4: 0 r_inf = max |r_i|, 1 r_sq = sum r_i^2, 2 bad (non-finite r_i, left out of 0 and 1), 3 0.0.
+ * z = zl - zu gives the optimality test, z = rbar with negate the right-hand side b1 of the KKT step.
+ * pk_ip_step_dev: dzl_i = (mu / dl - zl_i) - (zl_i / dl) dv_i, dzu_i = (mu / du - zu_i) + (zu_i / du) dv_i (0.0 on an absent or
+ * bad side) and a record of 4: 0 alpha_pri = min(1, (tau dl) / (-dv_i) over lower sides with dv_i < 0, (tau du) / dv_i over upper
+ * sides with dv_i > 0); 1 alpha_dual likewise from (tau zl) / (-dzl_i), dzl_i < 0, and (tau zu) / (-dzu_i), dzu_i < 0;
+ * 2 arg_pri, the smallest index that attains alpha_pri, -1.0 when alpha_pri is 1; 3 bad: bad sides, plus the elements with a
+ * side whose dv_i is not finite (counted once, left out).
+ * Every product and quotient is rounded before its sum (no fused multiply-add); the sums, maxima and minima are associated in
+ * a fixed way (pieces of 2048, the fixed tree, one scalar launch): no atomics, the same bits every run.  The _dev forms enqueue
+ * on `stream` (NULL: the context's) and do not synchronise; d_out is a device array.  They share the context's one array of partial
+ * columns whatever the stream, so the calls of one context must be stream-ordered: enqueue them on one stream, or order the
+ * streams with events.  pk_ip_terms, pk_dual_residual (on
+ * pk_linearize's values) and pk_ip_step are the host forms: upload, the _dev form, download, one synchronisation.
+ * Errors: 110 a null device pointer; 117 J^T is not set; 118 no linearization; 119 a sharded context; 123 no bounds
+ * (pk_set_bounds); 134 which not 0 or 1, mu negative or not finite, tau outside (0, 1]; 136 no device memory; 60 a null host
+ * buffer.  Nothing is enqueued or written after a refusal. */
+int pk_ip_terms_dev(pk_ctx* ctx, int which, const double* d_v, const double* d_zl, const double* d_zu, double mu, double* d_sigma,
+                    double* d_rbar, double* d_out /* 8 */, void* stream);
+int pk_dual_residual_dev(pk_ctx* ctx, const double* d_jvals, const double* d_grad, const double* d_lam, const double* d_z /* or NULL */,
+                         int negate, double* d_r, double* d_out /* 4 */, void* stream);
+int pk_ip_step_dev(pk_ctx* ctx, int which, const double* d_v, const double* d_dv, const double* d_zl, const double* d_zu, double mu,
+                   double tau, double* d_dzl, double* d_dzu, double* d_out /* 4 */, void* stream);
+int pk_ip_terms(pk_ctx* ctx, int which, const double* v, const double* zl, const double* zu, double mu, double* sigma, double* rbar,
+                double* out /* 8 */);
+int pk_dual_residual(pk_ctx* ctx, const double* grad, const double* lam, const double* z /* or NULL */, int negate, double* r,
+                     double* out /* 4 */);
+int pk_ip_step(pk_ctx* ctx, int which, const double* v, const double* dv, const double* zl, const double* zu, double mu, double tau,
+               double* dzl, double* dzu, double* out /* 4 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,14 @@ int pk_cg_step_dev(pk_ctx* ctx, int step, int64_t len, const double* d_b, const 
 int pk_minres_step_dev(pk_ctx* ctx, int step, int64_t len, int64_t split, const double* d_b, const double* d_x0, const double* d_minv,
                        const double* d_s1, const double* d_s2, double* d_x, double* d_r1, double* d_r2, double* d_y, double* d_v,
                        double* d_w, double* d_w2, double* d_q, double* d_rec, double tol, void* stream);
+/* ONE of the three vector kernels of pk_ipm.cpp and the scalar launch behind it on an EXPLICIT length with caller-owned device
+ * bounds d_lb, d_ub (the public forms call them with the context's bounds and n or m).  The partial columns are the context's.
+ * kind: 0 terms -- d_v, d_zl, d_zu, mu; writes sigma to d_o1, rbar to d_o2, the record of 8 to d_out; 1 residual -- d_t (may be
+ * d_o1 itself), d_z or NULL, negate; writes r to d_o1, the record of 4; 2 step -- d_v, d_dv, d_zl, d_zu, mu, tau; writes dzl to
+ * d_o1, dzu to d_o2, the record of 4.  Pointers a kind does not use may be NULL.  Errors 110, 134 for kind, len, mu or tau, 136. */
+int pk_ip_raw_dev(pk_ctx* ctx, int kind, int64_t len, const double* d_lb, const double* d_ub, const double* d_v, const double* d_dv,
+                  const double* d_zl, const double* d_zu, const double* d_t, const double* d_z, int negate, double mu, double tau,
+                  double* d_o1, double* d_o2, double* d_out, void* stream);
 
 #ifdef __cplusplus
 }

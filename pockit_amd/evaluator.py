@@ -1250,6 +1250,10 @@ class Evaluator:
         if self.src.sharded:
             raise NotImplementedError("the merit terms of a batch are not offered for a sharded evaluator")
         self._ensure_batch()
+        self._ensure_bounds()
+
+    def _ensure_bounds(self):
+        """The bounds on the device (the plan's unless ``set_bounds`` said otherwise), uploaded on first use."""
         if not self._bounds_up:
             if self._bounds is None:
                 self.set_bounds()
@@ -1315,6 +1319,76 @@ class Evaluator:
         dp = runtime.as_dp
         self.ctx.check(self.ctx.lib.pk_merit_scan(self.ctx.handle, len(a), dp(x), dp(d), dp(a), dp(out)))
         return out
+
+    # ------------------------------------------------------------------ barrier terms, dual residual, boundary step (csrc/pk_ipm.cpp)
+    WHICH = {"x": 0, "c": 1}      # the boxed vectors: the variables with v_lb, v_ub; the constraint rows' slacks with c_lb, c_ub
+
+    def _ensure_ipm(self):
+        """What every entry point of pk_ipm.cpp needs first: an unsharded evaluator and the bounds on the device (the plan's
+        unless ``set_bounds`` said otherwise).  The batched code object is not needed."""
+        if self.src.sharded:
+            raise NotImplementedError("the barrier terms, the dual residual and the boundary step are not offered for a sharded evaluator")
+        self._ensure_bounds()
+
+    def _which(self, which):
+        if which not in self.WHICH:
+            raise ValueError('which must be "x" (the variables) or "c" (the constraint rows)')
+        return self.WHICH[which], self.plan.n if which == "x" else self.plan.m
+
+    def ip_terms_dev(self, d_v, d_zl, d_zu, mu, d_sigma, d_rbar, d_out, which="x", stream=None):
+        """Enqueue ``sigma`` and ``rbar`` of the boxed vector at ``d_v`` with multipliers ``d_zl, d_zu`` and the record of 8
+        doubles at ``d_out`` (``BarrierTerms.COLUMNS``) on device pointers: two launches, not waited for."""
+        self._ensure_ipm()
+        self.ctx.check(self.ctx.lib.pk_ip_terms_dev(self.ctx.handle, self._which(which)[0], d_v, d_zl, d_zu, float(mu), d_sigma, d_rbar,
+                                                    d_out, stream))
+
+    def dual_residual_dev(self, d_jvals, d_grad, d_lam, d_r, d_out, d_z=None, negate=False, stream=None):
+        """Enqueue ``r = J^T lam + grad - z`` (negated with ``negate``; ``d_z`` None: no term; 0.0 for a fixed variable) and
+        the record of 4 doubles at ``d_out`` (``r_inf, r_sq, bad, 0``) on device pointers; ``d_jvals``: the CSR values of the
+        Jacobian map.  Not waited for."""
+        self._ensure_ipm()
+        self._operator("JT")
+        self.ctx.check(self.ctx.lib.pk_dual_residual_dev(self.ctx.handle, d_jvals, d_grad, d_lam, d_z, int(bool(negate)), d_r, d_out,
+                                                         stream))
+
+    def ip_step_dev(self, d_v, d_dv, d_zl, d_zu, mu, tau, d_dzl, d_dzu, d_out, which="x", stream=None):
+        """Enqueue the multiplier steps ``dzl, dzu`` of the step ``d_dv`` and the record of 4 doubles at ``d_out``
+        (``alpha_pri, alpha_dual, arg_pri, bad``) on device pointers: two launches, not waited for."""
+        self._ensure_ipm()
+        self.ctx.check(self.ctx.lib.pk_ip_step_dev(self.ctx.handle, self._which(which)[0], d_v, d_dv, d_zl, d_zu, float(mu), float(tau),
+                                                   d_dzl, d_dzu, d_out, stream))
+
+    def _boxed(self, count, **arrays):
+        out = []
+        for name, a in arrays.items():
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (count,):
+                raise ValueError(f"{name} must have shape ({count},)")
+            out.append(a)
+        return out
+
+    def barrier_terms(self, v, zl, zu, mu, which="x"):
+        """``BarrierTerms`` of the boxed vector ``v`` (``which``: "x" the variables, "c" the constraint rows' slacks) with the
+        multipliers ``zl, zu`` of its lower and upper sides and the barrier parameter ``mu``: one round trip."""
+        w, count = self._which(which)
+        v, zl, zu = self._boxed(count, v=v, zl=zl, zu=zu)
+        self._ensure_ipm()
+        sigma, rbar, rec = np.empty(count), np.empty(count), np.empty(8)
+        dp = runtime.as_dp
+        self.ctx.check(self.ctx.lib.pk_ip_terms(self.ctx.handle, w, dp(v), dp(zl), dp(zu), float(mu), dp(sigma), dp(rbar), dp(rec)))
+        return BarrierTerms(sigma, rbar, rec)
+
+    def boundary_step(self, v, dv, zl, zu, mu, tau=0.99, which="x"):
+        """``BoundaryStep`` of the step ``dv`` from ``v``: the multiplier steps and the fraction-to-the-boundary step lengths
+        with parameter ``tau`` in (0, 1].  One round trip."""
+        w, count = self._which(which)
+        v, dv, zl, zu = self._boxed(count, v=v, dv=dv, zl=zl, zu=zu)
+        self._ensure_ipm()
+        dzl, dzu, rec = np.empty(count), np.empty(count), np.empty(4)
+        dp = runtime.as_dp
+        self.ctx.check(self.ctx.lib.pk_ip_step(self.ctx.handle, w, dp(v), dp(dv), dp(zl), dp(zu), float(mu), float(tau), dp(dzl), dp(dzu),
+                                               dp(rec)))
+        return BoundaryStep(dzl, dzu, rec)
 
     def batch_launches(self):
         """Launches of ``pk_cycleb`` by this evaluator so far: a batch served by the loop of single cycles adds none."""
@@ -1434,6 +1508,73 @@ class MinresInfo:
 
     def __repr__(self):
         return f"MinresInfo(status={self.status!r}, iterations={self.iterations}, rel_residual={self.rel_residual:.3e})"
+
+
+class _Record:
+    """A read-only result: named views of a record of doubles (``COLUMNS``) beside its vectors."""
+    COLUMNS = ()
+    __slots__ = ("_rec", "_vectors")
+
+    def __init__(self, rec, **vectors):
+        rec = np.array(rec, dtype=np.float64)
+        rec.setflags(write=False)
+        for v in vectors.values():
+            v.setflags(write=False)
+        object.__setattr__(self, "_rec", rec)
+        object.__setattr__(self, "_vectors", vectors)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is read-only")
+
+    def __getattr__(self, name):
+        if name in type(self).COLUMNS:
+            return float(self._rec[type(self).COLUMNS.index(name)])
+        vectors = object.__getattribute__(self, "_vectors")
+        if name in vectors:
+            return vectors[name]
+        raise AttributeError(name)
+
+    table = property(lambda self: self._rec)
+
+    def __repr__(self):
+        return f"{type(self).__name__}(" + ", ".join(f"{k}={getattr(self, k):.6g}" for k in type(self).COLUMNS if not k.startswith("_")) + ")"
+
+
+class BarrierTerms(_Record):
+    """What ``Evaluator.barrier_terms`` reports (read-only): the vectors ``sigma`` and ``rbar``, the columns of the record by
+    name (``COLUMNS``; ``bad`` > 0: some side has a slack that is not positive or a multiplier that is negative or not finite
+    and was left out), ``table`` the record itself, ``mean_compl = compl_sum / sides``."""
+    COLUMNS = ("compl_inf", "compl_sum", "sides", "min_slack", "log_sum", "bad", "z_sum", "min_compl")
+    __slots__ = ()
+
+    def __init__(self, sigma, rbar, rec):
+        super().__init__(rec, sigma=sigma, rbar=rbar)
+
+    @property
+    def mean_compl(self):
+        return float(self._rec[1] / self._rec[2]) if self._rec[2] > 0 else 0.0
+
+
+class BoundaryStep(_Record):
+    """What ``Evaluator.boundary_step`` reports (read-only): the multiplier steps ``dzl, dzu``, the step lengths
+    ``alpha_primal`` and ``alpha_dual`` in (0, 1], ``blocking`` (the smallest index that limits the primal step, None when the
+    step is 1) and ``bad``; ``table`` is the record."""
+    COLUMNS = ("alpha_primal", "alpha_dual", "_arg", "bad")
+    __slots__ = ()
+
+    def __init__(self, dzl, dzu, rec):
+        super().__init__(rec, dzl=dzl, dzu=dzu)
+
+    @property
+    def blocking(self):
+        return None if self._rec[2] < 0 else int(self._rec[2])
+
+
+class DualResidual(_Record):
+    """What ``Linearization.dual_residual`` reports beside ``r`` (read-only): ``inf = max |r_i|``, ``two_sq = sum r_i^2`` and
+    ``bad`` (non-finite entries of r, left out of the other two); ``table`` is the record."""
+    COLUMNS = ("inf", "two_sq", "bad", "_zero")
+    __slots__ = ()
 
 
 class Linearization:
@@ -1717,6 +1858,23 @@ class Linearization:
                                              runtime.as_dp(b), self._opt(x0), float(tol), int(2 * size if maxiter is None else maxiter),
                                              int(check_every), runtime.as_dp(x), runtime.as_dp(rec)))
         return x, MinresInfo(rec, tol, x, self.n)
+
+    # ---- the dual side of optimality, and the first block of the KKT right-hand side (csrc/pk_ipm.cpp)
+    def dual_residual(self, grad, lam, z=None, negate=False):
+        """``r = J^T lam + grad - z`` on the device, negated with ``negate``; ``z`` None: no term; ``r_i = 0.0`` for a fixed
+        variable.  ``z = zl - zu`` gives the optimality test, ``z = rbar`` with ``negate`` the KKT step's ``b1``.  Returns
+        ``(r, DualResidual)``.  One round trip."""
+        ev = self._check_live(False)
+        grad, = ev._boxed(self.n, grad=grad)
+        lam, = ev._boxed(self.m, lam=lam)
+        if z is not None:
+            z, = ev._boxed(self.n, z=z)
+        ev._ensure_ipm()
+        ev._operator("JT")
+        r, rec = np.empty(self.n), np.empty(4)
+        dp = runtime.as_dp
+        ev.ctx.check(ev.ctx.lib.pk_dual_residual(ev.ctx.handle, dp(grad), dp(lam), self._opt(z), int(bool(negate)), dp(r), dp(rec)))
+        return r, DualResidual(rec)
 
     def jacobian_operator(self):
         from scipy.sparse.linalg import LinearOperator

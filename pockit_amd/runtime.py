@@ -137,6 +137,12 @@ PROTOTYPES = {
     "pk_minres_advance_dev": (C.c_int, [vp, C.c_int, vp]),
     "pk_minres_record": (C.c_int, [vp, dp]),
     "pk_solve_kkt": (C.c_int, [vp, C.c_int, dp, dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_int, dp, dp]),
+    "pk_ip_terms_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, C.c_double, vp, vp, vp, vp]),
+    "pk_dual_residual_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+    "pk_ip_step_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp]),
+    "pk_ip_terms": (C.c_int, [vp, C.c_int, dp, dp, dp, C.c_double, dp, dp, dp]),
+    "pk_dual_residual": (C.c_int, [vp, dp, dp, dp, C.c_int, dp, dp]),
+    "pk_ip_step": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, C.c_double, C.c_double, dp, dp, dp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -202,6 +208,8 @@ PROTOTYPES = {
     "pk_cg_step_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, vp]),
     "pk_minres_step_dev": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                      C.c_double, vp]),
+    "pk_ip_raw_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp,
+                                vp]),
 }
 EXPORTS = list(PROTOTYPES)
 
