@@ -463,6 +463,55 @@ int pk_dual_residual(pk_ctx* ctx, const double* grad, const double* lam, const d
 int pk_ip_step(pk_ctx* ctx, int which, const double* v, const double* dv, const double* zl, const double* zu, double mu, double tau,
                double* dzl, double* dzu, double* out /* 4 */);
 
+/* THE SLACKS OF A RESIDENT PRIMAL-DUAL ITERATE (kernels pk_sl_reduce_k, pk_sl_recover_k, pk_sl_update_k, pk_sl_merit_k,
+ * pk_sl_scalar_k of the library; pk_slack.cpp).  Rows are classified as the boxed vector which = 1 above:
+ * c_lb == c_ub is an EQUALITY row (no slack; nothing of s, of the slack's barrier terms or of its multipliers is read there), any
+ * other row an INEQUALITY row g_i - s_i = 0 whose slack s_i is boxed by the finite ones of c_lb_i, c_ub_i.  A fixed variable
+ * (v_lb == v_ub) takes part in nothing.  sigma_s, rbar_s are what pk_ip_terms_dev (which = 1) wrote for the slacks.
+ * pk_slack_reduce_dev: the slacks out of the step's system [[H + Sigma_x, J^T], [J, -S2]] (dx, dlam) = (b1, b2).  Equality row:
+ * s2_i = 0.0, b2_i = -(g_i - c_lb_i); inequality row: s2_i = 1 / sigma_s_i, b2_i = (-(g_i - s_i)) + s2_i (lam_i + rbar_s_i).
+ * A sigma_s_i that is not > 0 or not finite is bad: counted, s2_i = b2_i = 0.0.  A record of 4: 0 theta_inf = max |g - c|,
+ * |g - s|; 1 theta_1, their sum; 2 bad (bad sigma_s_i and residuals that are not finite, both left out of 0 and 1); 3 the
+ * inequality rows, counted.  s2 and b2 feed pk_minres_begin_dev / pk_solve_kkt as they are.
+ * pk_slack_recover_dev: ds_i = s2_i ((dlam_i + lam_i) + rbar_s_i) on inequality rows, 0.0 on equality rows and on a bad
+ * sigma_s_i, and the terms of the inertia-free curvature test with w = H dx (pk_apply_operator_dev) and s1 = Sigma_x: a record of
+ * 5 over the free variables and the inequality rows: 0 sum (dx_i w_i + s1_i dx_i^2); 1 sum sigma_s_i ds_i^2; 2 sum dx_i^2;
+ * 3 sum ds_i^2; 4 bad (bad sigma_s_i, terms that are not finite; left out).  The test is rec0 + rec1 >= kappa (rec2 + rec3).
+ * pk_slack_update_dev, IN PLACE on a boxed vector (which as above): v_i += alpha_p dv_i where not fixed; on a present side
+ * z_i += alpha_d dz_i, then with the NEW slack d the safeguard z_i = min(max(z_i, mu / (kappa d)), (kappa mu) / d); an absent
+ * side is neither read nor written.  With d_lam, d_dlam (both or neither; which = 1 only, else 134): lam_i += alpha_p dlam_i on
+ * every row.  A record of 4: 0 clamped multipliers; 1 the smallest new slack (+inf without a side); 2 bad: a new v_i or lam_i
+ * that is not finite, a new slack that is not > 0, a new multiplier that is not finite -- stored as computed, not clamped;
+ * 3 0.0.
+ * pk_slack_merit_dev: count trial points X (count x n, as pk_trial_points_dev wrote them) with their constraint values G
+ * (count x m) and the slacks s + alphas[b] ds; per entry 4 doubles: 0 theta_1 = sum_eq |g - c| + sum_ineq |g - (s + alpha ds)|;
+ * 1 theta_inf; 2 log_sum over the present sides of X[b] and of the slacks; 3 bad (a side whose slack is not > 0 or not finite, a
+ * residual that is not finite; left out).
+ * Arithmetic, association, streams and synchronisation as for pk_ip_terms_dev above: every product and quotient rounded on its
+ * own, pieces of 2048, the fixed tree, one scalar launch (one workgroup per entry of a batch); no atomics, the same bits every
+ * run; the calls of one context must be stream-ordered.  pk_slack_reduce, pk_slack_recover and pk_slack_update are the host
+ * forms (pk_slack_update works in place on the host arrays; lam, dlam NULL or both).
+ * Errors: 110 a null device pointer; 119 a sharded context; 123 no bounds (pk_set_bounds); 134 which not 0 or 1, lam without
+ * which = 1, alpha_p or alpha_d outside [0, 1], mu negative or not finite, kappa below 1 or not finite, count < 1; 136 no device
+ * memory; 60 a null host buffer.  Nothing is enqueued or written after a refusal. */
+int pk_slack_reduce_dev(pk_ctx* ctx, const double* d_g, const double* d_s, const double* d_lam, const double* d_sigma_s,
+                        const double* d_rbar_s, double* d_s2, double* d_b2, double* d_out /* 4 */, void* stream);
+int pk_slack_recover_dev(pk_ctx* ctx, const double* d_dlam, const double* d_lam, const double* d_rbar_s, const double* d_s2,
+                         const double* d_sigma_s, const double* d_dx, const double* d_w, const double* d_s1, double* d_ds,
+                         double* d_out /* 5 */, void* stream);
+int pk_slack_update_dev(pk_ctx* ctx, int which, double* d_v, const double* d_dv, double* d_zl, const double* d_dzl, double* d_zu,
+                        const double* d_dzu, double* d_lam /* or NULL */, const double* d_dlam /* or NULL */, double alpha_p,
+                        double alpha_d, double mu, double kappa, double* d_out /* 4 */, void* stream);
+int pk_slack_merit_dev(pk_ctx* ctx, int32_t count, const double* d_X, const double* d_G, const double* d_s, const double* d_ds,
+                       const double* d_alphas, double* d_out /* 4 * count */, void* stream);
+int pk_slack_reduce(pk_ctx* ctx, const double* g, const double* s, const double* lam, const double* sigma_s, const double* rbar_s,
+                    double* s2, double* b2, double* out /* 4 */);
+int pk_slack_recover(pk_ctx* ctx, const double* dlam, const double* lam, const double* rbar_s, const double* s2,
+                     const double* sigma_s, const double* dx, const double* w, const double* s1, double* ds, double* out /* 5 */);
+int pk_slack_update(pk_ctx* ctx, int which, double* v, const double* dv, double* zl, const double* dzl, double* zu, const double* dzu,
+                    double* lam /* or NULL */, const double* dlam /* or NULL */, double alpha_p, double alpha_d, double mu,
+                    double kappa, double* out /* 4 */);
+
 #ifdef __cplusplus
 }
 #endif

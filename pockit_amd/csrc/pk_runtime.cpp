@@ -2,7 +2,7 @@
 //
 // This file is the CORE unit: context, model and problem set-up, the launch machinery, the device-pointer entry points, the
 // one-shot host-buffer entry points and the cycle.  Its siblings (pk_runtime.h lists them): pk_shim.cpp (host shim),
-// pk_pool.cpp (helper threads), pk_shard.cpp (sharding), pk_extras.cpp (CSR, mesh error, profiling), pk_ops.cpp (J, J^T, H times a vector), pk_reduce.cpp (reductions over their rows), pk_merit.cpp (merit terms), pk_cg.cpp (CG on the condensed matrices), pk_minres.cpp (MINRES on the augmented KKT system), pk_ipm.cpp (barrier terms, dual residual, boundary step), pk_solve.cpp (what the two solves share on the host), pk_error.cpp.
+// pk_pool.cpp (helper threads), pk_shard.cpp (sharding), pk_extras.cpp (CSR, mesh error, profiling), pk_ops.cpp (J, J^T, H times a vector), pk_reduce.cpp (reductions over their rows), pk_merit.cpp (merit terms), pk_cg.cpp (CG on the condensed matrices), pk_minres.cpp (MINRES on the augmented KKT system), pk_ipm.cpp (barrier terms, dual residual, boundary step), pk_slack.cpp (slack elimination, slack step, iterate update, merit terms with slacks), pk_solve.cpp (what the two solves share on the host), pk_error.cpp.
 //
 // Owns: the HIP context objects of one GPU (stream, loaded code object, kernel handles), the
 // device copies of the per-(model, mesh) tables, and device work buffers (x, lambda, outputs,
@@ -32,7 +32,7 @@ void drop_cycle_graph(pk_ctx* c) {
 
 namespace {
 
-// every area frees what it owns (free_shim: pk_shim.cpp; free_mesh_error, free_csr, free_trace: pk_extras.cpp; free_operators: pk_ops.cpp; free_merit: pk_merit.cpp; free_ipm: pk_ipm.cpp; solve_free: pk_runtime.h)
+// every area frees what it owns (free_shim: pk_shim.cpp; free_mesh_error, free_csr, free_trace: pk_extras.cpp; free_operators: pk_ops.cpp; free_merit: pk_merit.cpp; free_ipm: pk_ipm.cpp; free_slack: pk_slack.cpp; solve_free: pk_runtime.h)
 void free_problem(pk_ctx* c) {
   release(c->d_items_jacc); release(c->d_Jc);
   release(c->d_phases); release(c->d_tiles); release(c->d_kinds); release(c->d_items_jac); release(c->d_items_hess); release(c->d_items_aux); release(c->d_outer); release(c->d_aux); release(c->d_items_hessc); release(c->d_Hc);
@@ -52,6 +52,7 @@ void free_problem(pk_ctx* c) {
   solve_free(c->cg);
   solve_free(c->minres);
   free_ipm(c);
+  free_slack(c);
   free_shim(c);
   c->have_problem = false;
 }

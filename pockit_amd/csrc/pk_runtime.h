@@ -18,11 +18,14 @@
 //                   (pk_mr_init, pk_mr_dot, pk_mr_update, pk_mr_scalar, pk_mr_elem: the library's own kernels)
 //   pk_ipm.cpp      barrier terms, dual residual and the step to the boundary of a boxed vector, around that solve (pk_ip_terms_k,
 //                   pk_ip_resid_k, pk_ip_step_k, pk_ip_scalar_k: the library's own kernels)
+//   pk_slack.cpp    the slacks of a resident iterate: their elimination, their step with the curvature terms, the update with the
+//                   multiplier safeguard, the merit terms of trial points with slacks (pk_sl_reduce_k, pk_sl_recover_k,
+//                   pk_sl_update_k, pk_sl_merit_k, pk_sl_scalar_k: the library's own kernels)
 //   pk_solve.cpp    the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp: the context's growing
-//                   arrays (lib_reserve, also pk_merit.cpp's and pk_ipm.cpp's), the common checks, the skeletons of record / advance / the host loop
+//                   arrays (lib_reserve, also pk_merit.cpp's, pk_ipm.cpp's and pk_slack.cpp's), the common checks, the skeletons of record / advance / the host loop
 //   pk_error.cpp    fail(): where an error message is kept
 //
-// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp, pk_minres.cpp and pk_ipm.cpp share
+// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp, pk_minres.cpp, pk_ipm.cpp and pk_slack.cpp share
 // beyond it: the scaffolding of kernels that are compiled into the library (function macro, tree driver, grid rule, host walk,
 // launch) and the pieced dot of the two solvers (piece size, tree step, partial store, scalar trip, their host stand-ins).
 //
@@ -210,6 +213,15 @@ struct PkIpm {
   size_t scratch_cap = 0;
 };
 
+// ---- slack elimination, slack step, iterate update and merit terms with slacks (pk_slack.cpp: pk_slack_reduce_dev ...; free_slack)
+// Allocated on first use; both arrays grow when needed and never shrink short of pk_set_problem.
+struct PkSlack {
+  double* d_partial = nullptr;      // the pieces' partial columns, planes x n_pieces doubles per entry of a batch (pk_libkernel.h)
+  size_t partial_cap = 0;
+  double* d_scratch = nullptr;      // the host forms' nine slices of max(n, m) doubles and the record of 8 behind them
+  size_t scratch_cap = 0;
+};
+
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
 struct PkMeshError {
   void* d_iv = nullptr;
@@ -365,6 +377,7 @@ struct pk_ctx : pk_error_state {
   PkMeshError mesh_error;
   PkShim shim;
   PkIpm ipm;         // (last: the members the cycle's host path reads keep the offsets they had)
+  PkSlack slack;     // (behind it, for the same reason)
 };
 
 #pragma GCC visibility push(hidden)      // (no function declared here leaves the library: its exports are the two C headers')
@@ -456,6 +469,9 @@ void free_merit(pk_ctx* c);          // bounds, partial rows and scratch (with t
 
 // ---- pk_ipm.cpp
 void free_ipm(pk_ctx* c);            // partial columns and scratch (with the problem)
+
+// ---- pk_slack.cpp
+void free_slack(pk_ctx* c);          // partial columns and scratch (with the problem)
 
 // ---- pk_solve.cpp: the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp (no kernels)
 // An array of the context that grows when needed and never shrinks: the new one first, so the error (code: 127 for the merit

@@ -238,6 +238,15 @@ int pk_minres_step_dev(pk_ctx* ctx, int step, int64_t len, int64_t split, const 
 int pk_ip_raw_dev(pk_ctx* ctx, int kind, int64_t len, const double* d_lb, const double* d_ub, const double* d_v, const double* d_dv,
                   const double* d_zl, const double* d_zu, const double* d_t, const double* d_z, int negate, double mu, double tau,
                   double* d_o1, double* d_o2, double* d_out, void* stream);
+/* ONE of the four vector kernels of pk_slack.cpp and the scalar launch behind it on EXPLICIT lengths n, m with caller-owned device
+ * bounds (the public forms call them with the context's).  The partial columns are the context's.  d_p: a HOST array of 10
+ * device pointers, by kind: 0 reduce -- g, s, lam, sigma_s, rbar_s, s2 (out), b2 (out); 1 recover -- dlam, lam, rbar_s, s2,
+ * sigma_s, dx, w, s1, ds (out); 2 update -- v, dv, zl, dzl, zu, dzu, lam or NULL, dlam or NULL, on the boxed vector of length m
+ * with bounds d_clb, d_cub; 3 merit -- X, G, s, ds, alphas, with `batch` entries.  Slots a kind does not use may be NULL, and so
+ * may d_xlb, d_xub for kinds 0 and 2.  Errors 110, 134 for kind, lengths, batch, alpha_p, alpha_d, mu or kappa, 136. */
+int pk_slack_raw_dev(pk_ctx* ctx, int kind, int64_t n, int64_t m, int64_t batch, const double* d_xlb, const double* d_xub,
+                     const double* d_clb, const double* d_cub, double* const* d_p, double alpha_p, double alpha_d, double mu, double kappa,
+                     double* d_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1390,6 +1390,83 @@ class Evaluator:
                                                dp(rec)))
         return BoundaryStep(dzl, dzu, rec)
 
+    # ------------------------------------------------------------------ the slacks of a resident iterate (csrc/pk_slack.cpp)
+    def slack_reduce_dev(self, d_g, d_s, d_lam, d_sigma_s, d_rbar_s, d_s2, d_b2, d_out, stream=None):
+        """Enqueue the elimination of the slacks on device pointers: ``s2`` and ``b2`` of the step's system
+        ``[[H + Sigma_x, J^T], [J, -S2]]`` from the constraint values ``d_g``, the slacks, the multipliers and the slacks'
+        ``sigma_s, rbar_s`` (``ip_terms_dev(..., which="c")``), and the record of 4 doubles at ``d_out``
+        (``SlackTerms.COLUMNS``): two launches, not waited for."""
+        self._ensure_ipm()
+        self.ctx.check(self.ctx.lib.pk_slack_reduce_dev(self.ctx.handle, d_g, d_s, d_lam, d_sigma_s, d_rbar_s, d_s2, d_b2, d_out, stream))
+
+    def slack_recover_dev(self, d_dlam, d_lam, d_rbar_s, d_s2, d_sigma_s, d_dx, d_w, d_s1, d_ds, d_out, stream=None):
+        """Enqueue the slacks' step ``ds = s2 ((dlam + lam) + rbar_s)`` and the record of 5 doubles at ``d_out``
+        (``SlackStep.COLUMNS``; ``d_w = H dx``, ``d_s1 = Sigma_x``) on device pointers: two launches, not waited for."""
+        self._ensure_ipm()
+        self.ctx.check(self.ctx.lib.pk_slack_recover_dev(self.ctx.handle, d_dlam, d_lam, d_rbar_s, d_s2, d_sigma_s, d_dx, d_w, d_s1, d_ds,
+                                                         d_out, stream))
+
+    def slack_update_dev(self, d_v, d_dv, d_zl, d_dzl, d_zu, d_dzu, alpha_p, alpha_d, mu, d_out, kappa=1e10, d_lam=None, d_dlam=None,
+                         which="x", stream=None):
+        """Enqueue the update IN PLACE of a boxed vector and its multipliers on device pointers: ``v += alpha_p dv``,
+        ``z += alpha_d dz`` and the safeguard ``z = min(max(z, mu / (kappa d)), kappa mu / d)`` with the new slacks; with
+        ``d_lam, d_dlam`` (``which="c"`` only) also ``lam += alpha_p dlam``.  The record of 4 doubles at ``d_out``:
+        ``IterateUpdate.COLUMNS``.  Two launches, not waited for."""
+        self._ensure_ipm()
+        self.ctx.check(self.ctx.lib.pk_slack_update_dev(self.ctx.handle, self._which(which)[0], d_v, d_dv, d_zl, d_dzl, d_zu, d_dzu, d_lam,
+                                                        d_dlam, float(alpha_p), float(alpha_d), float(mu), float(kappa), d_out, stream))
+
+    def slack_merit_dev(self, count, d_X, d_G, d_s, d_ds, d_alphas, d_out, stream=None):
+        """Enqueue the merit terms of ``count`` trial points with slacks on device pointers: per entry ``theta_1, theta_inf,
+        log_sum, bad`` at ``d_out`` (4 * count doubles) from the points ``d_X`` (count x n), their constraint values ``d_G``
+        (count x m) and the slacks ``s + alphas[b] ds``.  Two launches, not waited for."""
+        self._ensure_ipm()
+        self.ctx.check(self.ctx.lib.pk_slack_merit_dev(self.ctx.handle, int(count), d_X, d_G, d_s, d_ds, d_alphas, d_out, stream))
+
+    def slack_terms(self, g, s, lam, sigma_s, rbar_s):
+        """``SlackTerms`` of the constraint values ``g``, the slacks ``s``, the multipliers ``lam`` and the slacks' barrier terms
+        ``sigma_s, rbar_s`` (``barrier_terms(s, yl, yu, mu, which="c")``).  One round trip."""
+        m = self.plan.m
+        g, s, lam, sigma_s, rbar_s = self._boxed(m, g=g, s=s, lam=lam, sigma_s=sigma_s, rbar_s=rbar_s)
+        self._ensure_ipm()
+        s2, b2, rec = np.empty(m), np.empty(m), np.empty(4)
+        dp = runtime.as_dp
+        self.ctx.check(self.ctx.lib.pk_slack_reduce(self.ctx.handle, dp(g), dp(s), dp(lam), dp(sigma_s), dp(rbar_s), dp(s2), dp(b2), dp(rec)))
+        return SlackTerms(s2, b2, rec)
+
+    def slack_step(self, dlam, lam, rbar_s, s2, sigma_s, dx, w, s1):
+        """``SlackStep`` of the solve's ``dx, dlam``: the slacks' step and the terms of the curvature test; ``w = H dx``
+        (``Linearization.hv``), ``s1 = Sigma_x``.  One round trip."""
+        n, m = self.plan.n, self.plan.m
+        dlam, lam, rbar_s, s2, sigma_s = self._boxed(m, dlam=dlam, lam=lam, rbar_s=rbar_s, s2=s2, sigma_s=sigma_s)
+        dx, w, s1 = self._boxed(n, dx=dx, w=w, s1=s1)
+        self._ensure_ipm()
+        ds, rec = np.empty(m), np.empty(5)
+        dp = runtime.as_dp
+        self.ctx.check(self.ctx.lib.pk_slack_recover(self.ctx.handle, dp(dlam), dp(lam), dp(rbar_s), dp(s2), dp(sigma_s), dp(dx), dp(w), dp(s1),
+                                                     dp(ds), dp(rec)))
+        return SlackStep(ds, rec)
+
+    def update_iterate(self, v, dv, zl, dzl, zu, dzu, alpha_p, alpha_d, mu, kappa=1e10, lam=None, dlam=None, which="x"):
+        """``IterateUpdate``: copies of ``v, zl, zu`` (and ``lam``, with ``which="c"``) moved by the steps with the lengths
+        ``alpha_p`` (v, lam) and ``alpha_d`` (zl, zu), the multipliers safeguarded with the new slacks.  One round trip."""
+        w, count = self._which(which)
+        v, dv, zl, dzl, zu, dzu = self._boxed(count, v=v, dv=dv, zl=zl, dzl=dzl, zu=zu, dzu=dzu)
+        if (lam is None) != (dlam is None):
+            raise ValueError("lam and dlam go together")
+        if lam is not None:
+            if which != "c":
+                raise ValueError('lam goes with which="c" only')
+            lam, dlam = self._boxed(count, lam=lam, dlam=dlam)
+            lam = lam.copy()
+        self._ensure_ipm()
+        v, zl, zu, rec = v.copy(), zl.copy(), zu.copy(), np.empty(4)
+        dp = runtime.as_dp
+        opt = lambda a: None if a is None else dp(a)  # noqa: E731
+        self.ctx.check(self.ctx.lib.pk_slack_update(self.ctx.handle, w, dp(v), dp(dv), dp(zl), dp(dzl), dp(zu), dp(dzu), opt(lam), opt(dlam),
+                                                    float(alpha_p), float(alpha_d), float(mu), float(kappa), dp(rec)))
+        return IterateUpdate(v, zl, zu, lam, rec)
+
     def batch_launches(self):
         """Launches of ``pk_cycleb`` by this evaluator so far: a batch served by the loop of single cycles adds none."""
         n = C.c_int64()
@@ -1575,6 +1652,51 @@ class DualResidual(_Record):
     ``bad`` (non-finite entries of r, left out of the other two); ``table`` is the record."""
     COLUMNS = ("inf", "two_sq", "bad", "_zero")
     __slots__ = ()
+
+
+class SlackTerms(_Record):
+    """What ``Evaluator.slack_terms`` reports (read-only): the vectors ``s2`` and ``b2`` of the step's system with the slacks
+    eliminated, ``theta_inf`` and ``theta_1`` (the norms of ``g - c`` on equality rows and ``g - s`` on inequality rows), ``bad``
+    (a ``sigma_s`` that is not positive or a residual that is not finite, left out) and ``inequalities``, their count."""
+    COLUMNS = ("theta_inf", "theta_1", "bad", "inequalities")
+    __slots__ = ()
+
+    def __init__(self, s2, b2, rec):
+        super().__init__(rec, s2=s2, b2=b2)
+
+
+class SlackStep(_Record):
+    """What ``Evaluator.slack_step`` reports (read-only): the slacks' step ``ds`` and the terms of the inertia-free curvature
+    test -- ``curv_x = sum dx.w + s1.dx^2``, ``curv_s = sum sigma_s.ds^2``, ``dx_sq``, ``ds_sq`` and ``bad``;
+    ``curvature = curv_x + curv_s``, ``step_sq = dx_sq + ds_sq``, ``accepts(kappa)`` the test itself."""
+    COLUMNS = ("curv_x", "curv_s", "dx_sq", "ds_sq", "bad")
+    __slots__ = ()
+
+    def __init__(self, ds, rec):
+        super().__init__(rec, ds=ds)
+
+    curvature = property(lambda self: float(self._rec[0] + self._rec[1]))
+    step_sq = property(lambda self: float(self._rec[2] + self._rec[3]))
+
+    def accepts(self, kappa=1e-11):
+        return self.bad == 0.0 and self.curvature >= kappa * self.step_sq
+
+
+class IterateUpdate(_Record):
+    """What ``Evaluator.update_iterate`` reports (read-only): the updated ``v``, ``zl``, ``zu`` and ``lam`` (None when none was
+    given), ``clamped`` (multipliers the safeguard moved), ``min_slack`` (the smallest new slack) and ``bad``."""
+    COLUMNS = ("clamped", "min_slack", "bad", "_zero")
+    __slots__ = ()
+
+    def __init__(self, v, zl, zu, lam, rec):
+        vectors = dict(v=v, zl=zl, zu=zu)
+        if lam is not None:
+            vectors["lam"] = lam
+        super().__init__(rec, **vectors)
+
+    @property
+    def lam(self):
+        return self._vectors.get("lam")
 
 
 class Linearization:

@@ -143,6 +143,13 @@ PROTOTYPES = {
     "pk_ip_terms": (C.c_int, [vp, C.c_int, dp, dp, dp, C.c_double, dp, dp, dp]),
     "pk_dual_residual": (C.c_int, [vp, dp, dp, dp, C.c_int, dp, dp]),
     "pk_ip_step": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, C.c_double, C.c_double, dp, dp, dp]),
+    "pk_slack_reduce_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pk_slack_recover_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pk_slack_update_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]),
+    "pk_slack_merit_dev": (C.c_int, [vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]),
+    "pk_slack_reduce": (C.c_int, [vp, dp, dp, dp, dp, dp, dp, dp, dp]),
+    "pk_slack_recover": (C.c_int, [vp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
+    "pk_slack_update": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_double, dp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -210,6 +217,8 @@ PROTOTYPES = {
                                      C.c_double, vp]),
     "pk_ip_raw_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp,
                                 vp]),
+    "pk_slack_raw_dev": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
+                                   C.c_double, vp, vp]),
 }
 EXPORTS = list(PROTOTYPES)
 

@@ -1,0 +1,178 @@
+"""Host-landed time of ``interior_point.solve`` (direct) against ``optimizer.scipy.solve`` (trust-constr) on the brachistochrone,
+and of one resident round of the interior-point iteration (everything but the linear solve) against the same quantities in NumPy
+on downloaded vectors -- what a caller writes without the units.  Needs an MI355X; prints a table.
+
+    python tools/ip_solve_probe.py [--runs 5] [--out profiles/ip_solve_probe_mi355x.txt] [--quadrotor]
+"""
+import argparse
+import importlib
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+MODELS = [("brachistochrone", "radau", 10, 8), ("brachistochrone", "radau", 200, 8)]
+MU, TAU = 0.1, 0.99
+
+
+def spread(samples, scale=1.0, fmt="9.1f"):
+    return f"{statistics.median(samples) * scale:{fmt}} [{min(samples) * scale:.1f}, {max(samples) * scale:.1f}]"
+
+
+def resident_round(R, ipm):
+    """measure (terms of x and s at mu and at 0, r_d, slack_reduce) + b1 + H dx + slack_recover + ip_step of x and s + the merit of
+    two trial points' slacks; the updates are left out so that the round can be repeated on the same iterate.  Records down."""
+    ev, at, n = R.ev, R.at, R.n
+    q = R.measure(MU)
+    ev.dual_residual_dev(at(R.cj), at(R.grad), at(R.lam), at(R.rhs), at(R.rec, 40), d_z=at(R.rbar_x), negate=True)
+    ev.apply_operator_dev("H", at(R.ch), at(R.sol), at(R.w))
+    ev.slack_recover_dev(at(R.sol, n), at(R.lam), at(R.rbar_s), at(R.s2), at(R.sig_s), at(R.sol), at(R.w), at(R.sig_x), at(R.ds), at(R.rec, 44))
+    ev.ip_step_dev(at(R.x), at(R.sol), at(R.zl), at(R.zu), MU, TAU, at(R.dzl), at(R.dzu), at(R.rec, 52))
+    ev.ip_step_dev(at(R.s), at(R.ds), at(R.yl), at(R.yu), MU, TAU, at(R.dyl), at(R.dyu), at(R.rec, 56), which="c")
+    R.to_torch()
+    return q, R.down(R.rec)
+
+
+def numpy_round(R, J, H):
+    """The same quantities on downloaded vectors: x, s, lam, the four multipliers, g, grad and the step come down (J and H lie
+    on the host as SciPy matrices already), sigma_x, s2 and the right-hand side go up again."""
+    n, m = R.n, R.m
+    x, s, lam, zl, zu, yl, yu, g, grad = (R.down(t, c).copy() for t, c in ((R.x, n), (R.s, m), (R.lam, m), (R.zl, n), (R.zu, n), (R.yl, m),
+                                                                            (R.yu, m), (R.g, m), (R.grad, n)))
+    sol = R.down(R.sol, n + m).copy()
+    dx, dlam = sol[:n], sol[n:]
+    out = {}
+    with np.errstate(all="ignore"):
+        for name, v, lb, ub, a, b, dv in (("x", x, R.v_lb, R.v_ub, zl, zu, dx), ("s", s, R.c_lb, R.c_ub, yl, yu, None)):
+            boxed = lb != ub
+            lo, up = boxed & np.isfinite(lb), boxed & np.isfinite(ub)
+            dl, du = np.where(lo, v - lb, 1.0), np.where(up, ub - v, 1.0)
+            sigma = np.where(lo, a / dl, 0.0) + np.where(up, b / du, 0.0)
+            rbar = np.where(lo, MU / dl, 0.0) - np.where(up, MU / du, 0.0)
+            compl = max(np.max(np.abs(dl * a - MU), where=lo, initial=0.0), np.max(np.abs(du * b - MU), where=up, initial=0.0))
+            compl0 = max(np.max(dl * a, where=lo, initial=0.0), np.max(du * b, where=up, initial=0.0))
+            logs = np.sum(np.log(dl), where=lo) + np.sum(np.log(du), where=up)
+            out[name] = dict(lo=lo, up=up, dl=dl, du=du, sigma=sigma, rbar=rbar, compl=compl, compl0=compl0, logs=logs, z_sum=a[lo].sum() + b[up].sum())
+        ineq = R.c_lb != R.c_ub
+        r_d = np.where(R.free, J.T @ lam + grad - zl + zu, 0.0)
+        r_s = np.where(ineq, -lam - yl + yu, 0.0)
+        s2 = np.where(ineq, 1.0 / out["s"]["sigma"], 0.0)
+        res = np.where(ineq, g - s, g - R.c_lb)
+        b2 = -res + s2 * np.where(ineq, lam + out["s"]["rbar"], 0.0)
+        b1 = np.where(R.free, -(J.T @ lam + grad - out["x"]["rbar"]), 0.0)
+        ds = s2 * np.where(ineq, dlam + lam + out["s"]["rbar"], 0.0)
+        curv = dx @ (H @ dx) + out["x"]["sigma"] @ (dx * dx) + np.where(ineq, out["s"]["sigma"], 0.0) @ (ds * ds)
+        alphas = []
+        for name, dv, a, b in (("x", dx, zl, zu), ("s", ds, yl, yu)):
+            o = out[name]
+            dza = np.where(o["lo"], (MU / o["dl"] - a) - (a / o["dl"]) * dv, 0.0)
+            dzb = np.where(o["up"], (MU / o["du"] - b) + (b / o["du"]) * dv, 0.0)
+            cand = np.concatenate(((TAU * o["dl"])[o["lo"] & (dv < 0)] / -dv[o["lo"] & (dv < 0)], (TAU * o["du"])[o["up"] & (dv > 0)] / dv[o["up"] & (dv > 0)]))
+            cz = np.concatenate(((TAU * a)[o["lo"] & (dza < 0)] / -dza[o["lo"] & (dza < 0)], (TAU * b)[o["up"] & (dzb < 0)] / -dzb[o["up"] & (dzb < 0)]))
+            alphas.append((min(1.0, cand.min(initial=1.0)), min(1.0, cz.min(initial=1.0))))
+    R.s1 = R.up(out["x"]["sigma"])
+    R.s2 = R.up(s2)
+    R.rhs = R.up(np.concatenate((b1, b2)))
+    R.to_kernels()
+    return dict(r_d=np.abs(r_d).max(), r_s=np.abs(r_s).max(), theta=np.abs(res).max(), theta_1=np.abs(res).sum(), curv=curv, alphas=alphas,
+                compl=max(out["x"]["compl"], out["s"]["compl"]), compl0=max(out["x"]["compl0"], out["s"]["compl0"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quadrotor", action="store_true", help="also run planar_quadrotor(radau, 14, 6) once and report what happens")
+    ap.add_argument("--trust-constr-large", type=int, default=1, help="trust-constr runs on the large model (each takes minutes)")
+    ap.add_argument("--large-maxiter", type=int, default=400, help="trust-constr's maxiter on the large model")
+    args = ap.parse_args()
+    import models
+    from pockit_amd.optimizer import interior_point as ipm
+    from pockit_amd.optimizer import scipy as scipy_solver
+
+    lines = [f"ip_solve_probe: interior_point.solve (direct, tol 1e-8) against optimizer.scipy.solve (trust-constr, gtol 1e-9, xtol 1e-11); "
+             f"median [min, max] of {args.runs} alternating runs, host-landed (perf_counter around whole solves and around rounds that end in a wait)"]
+    for name, scheme, mesh, num_point in MODELS:
+        ns = importlib.import_module(f"pockit_amd.{scheme}")
+        system, _, guess = getattr(models, name)(ns, mesh, num_point)
+        large = system.plan.n > 2000
+        _, info = ipm.solve(system, guess)                                    # warm-up: code objects, the batch's self-check
+        t_ip, t_tc, its, tc_its, tc_f = [], [], [], [], []
+        for k in range(args.runs):
+            t0 = time.perf_counter()
+            _, info = ipm.solve(system, guess)
+            t1 = time.perf_counter()
+            t_ip.append(t1 - t0)
+            its.append(info["iterations"])
+            if not large or k < args.trust_constr_large:
+                t0 = time.perf_counter()
+                _, res = scipy_solver.solve(system, guess, {"maxiter": args.large_maxiter if large else 400, "gtol": 1e-9, "xtol": 1e-11})
+                t_tc.append(time.perf_counter() - t0)
+                tc_its.append(int(res.nit))
+                tc_f.append(float(res.fun))
+        lines.append(f"{name}({scheme}, {mesh}, {num_point}): n {system.plan.n}, m {system.plan.m}")
+        lines.append(f"    interior_point.solve (direct)   {spread(t_ip, 1e3)} ms, status {info['status']}, {its[-1]} Newton iterations, "
+                     f"{info['regularisations']} regularised, f = {info['obj_val']:.10f}, E_0 {info['error']:.2e}")
+        lines.append(f"    scipy trust-constr ({len(t_tc)} run{'s' if len(t_tc) != 1 else ''})    {spread(t_tc, 1e3)} ms, {tc_its[-1]} iterations (status {int(res.status)}: "
+                     f"0 is trust-constr's maxiter), f = {tc_f[-1]:.10f}")
+        # ---- one resident round against NumPy on downloaded vectors, at the start point with a unit step direction
+        R = ipm._Resident(system, ipm.preprocess(system, guess, None)[0])
+        R.evaluate()
+        R.to_torch()
+        R.s = R.up(np.where(R.ineq, ipm.push_inside(R.down(R.g, R.m), R.c_lb, R.c_ub), 0.0))
+        rng = np.random.default_rng(3)
+        R.sol = R.up(1e-3 * rng.standard_normal(R.n + R.m) * np.concatenate((R.free, np.ones(R.m))))
+        R.to_kernels()
+        J = R.map_j.to_scipy(R.down(R.cj, R.map_j.nnz).copy())
+        L = R.map_h.to_scipy(R.down(R.ch, R.map_h.nnz).copy())
+        import scipy.sparse as sp
+
+        H = (L + L.T - sp.diags(L.diagonal())).tocsr()
+        q, rec = resident_round(R, ipm)
+        ref = numpy_round(R, J, H)
+        agree = max(abs(q["rd"][0] - ref["r_d"]), abs(q["red"][0] - ref["theta"]), abs(rec[44] + rec[45] - ref["curv"]) / max(1.0, abs(ref["curv"])),
+                    abs(min(rec[52], rec[56]) - min(ref["alphas"][0][0], ref["alphas"][1][0])))
+        t_res, t_np = [], []
+        for _ in range(args.runs):
+            t0 = time.perf_counter()
+            resident_round(R, ipm)
+            t1 = time.perf_counter()
+            numpy_round(R, J, H)
+            t2 = time.perf_counter()
+            t_res.append(1e6 * (t1 - t0))
+            t_np.append(1e6 * (t2 - t1))
+        n, m = R.n, R.m
+        lines.append(f"    one round but the linear solve, resident (16 launches + 2 products, 3 waits, 512 bytes of records down) {spread(t_res)} us")
+        lines.append(f"    the same in NumPy: {8 * (3 * n + 6 * m + n + m)} bytes down, {8 * (2 * n + 2 * m)} bytes up    {spread(t_np)} us; "
+                     f"max difference of r_d, theta, curvature (relative), alpha_primal {agree:.2e}")
+        system.evaluator.close()
+    if args.quadrotor:
+        ns = importlib.import_module("pockit_amd.radau")
+        system, _, guess = models.planar_quadrotor(ns, 14, 6)
+        t0 = time.perf_counter()
+        _, info = ipm.solve(system, guess)
+        lines.append(f"planar_quadrotor(radau, 14, 6), direct, once: status {info['status']} ({info['status_msg']}), {info['iterations']} iterations, "
+                     f"{info['regularisations']} regularised, final E_0 {info['error']:.3e}, mu {info['mu']:.1e}, {time.perf_counter() - t0:.1f} s")
+        system.evaluator.close()
+        ns = importlib.import_module("pockit_amd.radau")
+        system, _, guess = models.brachistochrone(ns, 10, 8)
+        _, info = ipm.solve(system, guess, {"max_iter": 30}, linear_solver="minres")
+        lines.append(f"brachistochrone(radau, 10, 8), minres, max_iter 30, once: status {info['status']} ({info['status_msg']}), {info['iterations']} "
+                     f"Newton iterations, {info['linear_iterations']} MINRES iterations in all, final E_0 {info['error']:.3e}")
+        system.evaluator.close()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
