@@ -512,6 +512,33 @@ int pk_slack_update(pk_ctx* ctx, int which, double* v, const double* dv, double*
                     double* lam /* or NULL */, const double* dlam /* or NULL */, double alpha_p, double alpha_d, double mu,
                     double kappa, double* out /* 4 */);
 
+/* THE STEP'S SYSTEM FACTORED ON THE DEVICE: A BORDERED BAND LU (kernels pk_bd_init_k, pk_bd_fill_k, pk_bd_panel_k, pk_bd_update_k,
+ * pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k of the library; pk_band.cpp, DESIGN.md
+ * section 23).  K = [[H + diag(s1), J^T], [J, -diag(s2)]] over the free variables and all rows, permuted to [[B, U], [U^T, C]]:
+ * B (nb x nb) with half-bandwidth w in LAPACK's dgbtrf storage (kl = ku = w, leading dimension 3 w + 1), U nb x p and C p x p
+ * column-major, w <= 192, p <= 8.
+ * pk_band_plan uploads the plan once (it replaces an earlier one): order[k], k < nb + p, is the position in the caller's vectors
+ * of n + m values of the unknown at permuted position k (the border last); map holds two source codes per stored slot of
+ * [band | U | C] (0: none, +(e + 1): plus entry e of [hvals | jvals | s1 (n) | s2 (m)], -(e + 1): minus it; a slot is 0.0 plus its
+ * sources in this order).  The CSR maps must be set: the sources are checked against their sizes.
+ * pk_band_factor_dev fills the matrix from the resident arrays and factors B with partial pivoting inside the band (dgbtf2's
+ * arithmetic, every product rounded before it is subtracted; the same bits every run).  pk_band_solve_dev solves K sol = rhs on
+ * vectors of n + m values in the caller's order (fixed variables: rhs not read, sol 0.0).  Both enqueue on the context's stream
+ * and wait for nothing.  pk_band_record copies the record of 8 doubles and synchronises: 0 status (0 solved, 1 singular band
+ * pivot, 2 singular border, 3 non-finite); 1 the failing column in permuted numbering or -1; 2, 3 the smallest and largest
+ * |pivot|; 4 nb; 5 w; 6 p; 7 the interchanges that moved a row.  After status != 0 sol is left untouched.  Pivoting never leaves
+ * the band part: a K whose B is singular fails here though K is not.
+ * pk_solve_banded is the host form on pk_linearize's values: one upload of b, s1 and s2, factor, solve, one download of x (left
+ * untouched unless status is 0) and the record.
+ * Errors: 110 a null device pointer; 119 a sharded context; 136 no device memory; 60 a null host buffer; 134 nb < 0, w or p beyond
+ * the cap, an order or a map outside the system, factor or solve without a plan, solve or record without a factorisation; 117 an
+ * operator of the host form that is not set; 118 no linearization with a Hessian.  Nothing is enqueued or written after a refusal. */
+int pk_band_plan(pk_ctx* ctx, int64_t nb, int32_t w, int32_t p, const int32_t* order /* nb + p */, const int32_t* map /* 2 per slot */);
+int pk_band_factor_dev(pk_ctx* ctx, const double* d_hvals, const double* d_jvals, const double* d_s1, const double* d_s2);
+int pk_band_solve_dev(pk_ctx* ctx, const double* d_rhs, double* d_sol);
+int pk_band_record(pk_ctx* ctx, double* rec /* 8 */);
+int pk_solve_banded(pk_ctx* ctx, const double* s1, const double* s2, const double* b, double* x, double* rec /* 8 */);
+
 #ifdef __cplusplus
 }
 #endif

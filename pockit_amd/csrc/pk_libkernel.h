@@ -1,5 +1,5 @@
 // pk_libkernel.h -- private to the units whose kernels are compiled into the library itself, not into a model's code object
-// (pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp, pk_minres.cpp, pk_ipm.cpp, pk_slack.cpp): what such a unit needs around its own arithmetic, stated once
+// (pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp, pk_minres.cpp, pk_ipm.cpp, pk_slack.cpp, pk_band.cpp): what such a unit needs around its own arithmetic, stated once
 // -- function macro, grid rule, tree driver, launch, host walk -- and the pieced dot the two solvers share.
 //
 // A unit writes the work of one thread as PK_LIB_FN functions.  Under __HIPCC__ its kernels call them between barriers; without

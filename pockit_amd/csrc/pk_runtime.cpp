@@ -32,7 +32,7 @@ void drop_cycle_graph(pk_ctx* c) {
 
 namespace {
 
-// every area frees what it owns (free_shim: pk_shim.cpp; free_mesh_error, free_csr, free_trace: pk_extras.cpp; free_operators: pk_ops.cpp; free_merit: pk_merit.cpp; free_ipm: pk_ipm.cpp; free_slack: pk_slack.cpp; solve_free: pk_runtime.h)
+// every area frees what it owns (free_shim: pk_shim.cpp; free_mesh_error, free_csr, free_trace: pk_extras.cpp; free_operators: pk_ops.cpp; free_merit: pk_merit.cpp; free_ipm: pk_ipm.cpp; free_slack: pk_slack.cpp; free_band: pk_band.cpp; solve_free: pk_runtime.h)
 void free_problem(pk_ctx* c) {
   release(c->d_items_jacc); release(c->d_Jc);
   release(c->d_phases); release(c->d_tiles); release(c->d_kinds); release(c->d_items_jac); release(c->d_items_hess); release(c->d_items_aux); release(c->d_outer); release(c->d_aux); release(c->d_items_hessc); release(c->d_Hc);
@@ -53,6 +53,7 @@ void free_problem(pk_ctx* c) {
   solve_free(c->minres);
   free_ipm(c);
   free_slack(c);
+  free_band(c);
   free_shim(c);
   c->have_problem = false;
 }

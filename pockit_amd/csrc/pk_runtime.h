@@ -21,11 +21,14 @@
 //   pk_slack.cpp    the slacks of a resident iterate: their elimination, their step with the curvature terms, the update with the
 //                   multiplier safeguard, the merit terms of trial points with slacks (pk_sl_reduce_k, pk_sl_recover_k,
 //                   pk_sl_update_k, pk_sl_merit_k, pk_sl_scalar_k: the library's own kernels)
+//   pk_band.cpp     the step's system assembled, factored and solved on the device: a band LU with partial pivoting inside the
+//                   band, bordered by the few dense unknowns (pk_bd_init_k, pk_bd_fill_k, pk_bd_panel_k, pk_bd_update_k,
+//                   pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k: the library's own kernels)
 //   pk_solve.cpp    the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp: the context's growing
-//                   arrays (lib_reserve, also pk_merit.cpp's, pk_ipm.cpp's and pk_slack.cpp's), the common checks, the skeletons of record / advance / the host loop
+//                   arrays (lib_reserve, also pk_merit.cpp's, pk_ipm.cpp's, pk_slack.cpp's and pk_band.cpp's), the common checks, the skeletons of record / advance / the host loop
 //   pk_error.cpp    fail(): where an error message is kept
 //
-// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp, pk_minres.cpp, pk_ipm.cpp and pk_slack.cpp share
+// pk_libkernel.h, on top of this header, is what pk_ops.cpp, pk_reduce.cpp, pk_merit.cpp, pk_cg.cpp, pk_minres.cpp, pk_ipm.cpp, pk_slack.cpp and pk_band.cpp share
 // beyond it: the scaffolding of kernels that are compiled into the library (function macro, tree driver, grid rule, host walk,
 // launch) and the pieced dot of the two solvers (piece size, tree step, partial store, scalar trip, their host stand-ins).
 //
@@ -222,6 +225,24 @@ struct PkSlack {
   size_t scratch_cap = 0;
 };
 
+// ---- the bordered band LU of the step's system (pk_band.cpp: pk_band_plan, pk_band_factor_dev, pk_band_solve_dev ...; free_band)
+// The plan's arrays are replaced by the next plan; the others grow when needed and never shrink short of pk_set_problem.
+struct PkBand {
+  int32_t *d_map = nullptr, *d_order = nullptr, *d_where = nullptr;   // pk_band_plan: two source codes per stored slot, the caller's
+                                                                      // index of a permuted position, and its inverse (n + m)
+  double* d_work = nullptr;         // [band | U | C | Y | x | b_C | record] of the planned system
+  double* d_ipiv = nullptr;         // the interchanges (Nb 32-bit integers)
+  double* d_partial = nullptr;      // the pieces' partial sums of the border's dots, (p + 1) p planes x n_pieces doubles
+  size_t partial_cap = 0;
+  double* d_scratch = nullptr;      // the host form's [b | s1 s2 | x]
+  size_t scratch_cap = 0;
+  double* d_raw = nullptr;          // pk_band_raw_dev's [Y | x | b_C | record]
+  size_t raw_cap = 0;
+  int64_t nb = 0, w = 0, p = 0;
+  int64_t sources = 0;              // entries of [hvals | jvals | s1 | s2] the plan was checked against
+  bool planned = false, factored = false;
+};
+
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
 struct PkMeshError {
   void* d_iv = nullptr;
@@ -378,6 +399,7 @@ struct pk_ctx : pk_error_state {
   PkShim shim;
   PkIpm ipm;         // (last: the members the cycle's host path reads keep the offsets they had)
   PkSlack slack;     // (behind it, for the same reason)
+  PkBand band;       // (and behind that)
 };
 
 #pragma GCC visibility push(hidden)      // (no function declared here leaves the library: its exports are the two C headers')
@@ -472,6 +494,9 @@ void free_ipm(pk_ctx* c);            // partial columns and scratch (with the pr
 
 // ---- pk_slack.cpp
 void free_slack(pk_ctx* c);          // partial columns and scratch (with the problem)
+
+// ---- pk_band.cpp
+void free_band(pk_ctx* c);           // the plan and every array of the unit (with the problem)
 
 // ---- pk_solve.cpp: the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp (no kernels)
 // An array of the context that grows when needed and never shrinks: the new one first, so the error (code: 127 for the merit

@@ -247,6 +247,15 @@ int pk_ip_raw_dev(pk_ctx* ctx, int kind, int64_t len, const double* d_lb, const 
 int pk_slack_raw_dev(pk_ctx* ctx, int kind, int64_t n, int64_t m, int64_t batch, const double* d_xlb, const double* d_xub,
                      const double* d_clb, const double* d_cub, double* const* d_p, double alpha_p, double alpha_d, double mu, double kappa,
                      double* d_out, void* stream);
+/* The factorisation and the solve of pk_band.cpp on a CALLER-GIVEN matrix already in band storage: d_band (ldab x nb, ldab =
+ * 3 w + 1, factored in place), d_U (nb x p) and d_C (p x p) column-major (NULL allowed for p = 0), d_rhs and d_x of nb + p values in
+ * permuted order ([band part | border]), d_ipiv nb 32-bit integers, d_rec the record of 8.  R, the right-hand sides of the
+ * band solve, is p + 1.  The work arrays are the context's; enqueued on its stream.  Errors 110, 134, 136. */
+/* The fill of the planned system alone (pk_bd_fill_k) into a caller's array of as many doubles as the plan has stored slots,
+ * [band | U | C]: what pk_band_factor_dev factors.  Errors 110, 119, 134 without a plan. */
+int pk_band_fill_dev(pk_ctx* ctx, const double* d_hvals, const double* d_jvals, const double* d_s1, const double* d_s2, double* d_out);
+int pk_band_raw_dev(pk_ctx* ctx, int64_t nb, int32_t w, int32_t p, int32_t R, double* d_band, const double* d_U, const double* d_C,
+                    const double* d_rhs, int32_t* d_ipiv, double* d_x, double* d_rec);
 
 #ifdef __cplusplus
 }

@@ -1390,6 +1390,36 @@ class Evaluator:
                                                dp(rec)))
         return BoundaryStep(dzl, dzu, rec)
 
+    # ------------------------------------------------------------------ the step's system factored on the device (csrc/pk_band.cpp)
+    def band_plan(self, ordering):
+        """Upload the plan of the bordered band LU once: the permutation, the border, the half-bandwidth and the assembly map of
+        a ``pockit_amd.band.BandOrdering`` built from this evaluator's CSR maps.  It replaces an earlier plan."""
+        if self.src.sharded:
+            raise NotImplementedError("the band factorisation is not offered for a sharded evaluator")
+        self.csr_map("jac")
+        self.csr_map("hess")
+        order = np.ascontiguousarray(ordering.order, dtype=np.int32)
+        amap = np.ascontiguousarray(ordering.map, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.pk_band_plan(self.ctx.handle, int(ordering.nb), int(ordering.w), int(ordering.p),
+                                                 order.ctypes.data_as(runtime.c_int32_p), amap.ctypes.data_as(runtime.c_int32_p)))
+
+    def band_factor_dev(self, d_hvals, d_jvals, d_s1, d_s2):
+        """Enqueue the assembly of ``K = [[H + diag(s1), J^T], [J, -diag(s2)]]`` from the resident CSR values and ``s1`` (n),
+        ``s2`` (m) on device pointers, and its band LU with partial pivoting inside the band.  Not waited for."""
+        self.ctx.check(self.ctx.lib.pk_band_factor_dev(self.ctx.handle, d_hvals, d_jvals, d_s1, d_s2))
+
+    def band_solve_dev(self, d_rhs, d_sol):
+        """Enqueue the solve ``K sol = rhs`` with the factors of ``band_factor_dev`` on device vectors of n + m values (fixed
+        variables get 0.0).  Not waited for; after a failed factorisation ``d_sol`` is left untouched."""
+        self.ctx.check(self.ctx.lib.pk_band_solve_dev(self.ctx.handle, d_rhs, d_sol))
+
+    def band_record(self):
+        """The record of the last factorisation and solve (8 doubles: status, failing column, smallest and largest |pivot|,
+        Nb, w, p, interchanges), waited for."""
+        rec = np.empty(8)
+        self.ctx.check(self.ctx.lib.pk_band_record(self.ctx.handle, runtime.as_dp(rec)))
+        return rec
+
     # ------------------------------------------------------------------ the slacks of a resident iterate (csrc/pk_slack.cpp)
     def slack_reduce_dev(self, d_g, d_s, d_lam, d_sigma_s, d_rbar_s, d_s2, d_b2, d_out, stream=None):
         """Enqueue the elimination of the slacks on device pointers: ``s2`` and ``b2`` of the step's system
@@ -1585,6 +1615,40 @@ class MinresInfo:
 
     def __repr__(self):
         return f"MinresInfo(status={self.status!r}, iterations={self.iterations}, rel_residual={self.rel_residual:.3e})"
+
+
+class BandInfo:
+    """What a band factorisation and solve on the device reports (read-only): ``status`` by name, ``column`` (the failing
+    column in permuted numbering, -1 without one), ``min_pivot`` and ``max_pivot`` (of the band part), ``width``, ``border``,
+    ``interchanges`` (columns whose pivot moved a row), ``primal`` and ``dual`` (views of the solution's two blocks) and the raw
+    ``record`` of 8 doubles."""
+    STATUS = {0: "solved", 1: "singular_band_pivot", 2: "singular_border", 3: "non_finite"}
+    __slots__ = ("_rec", "_x", "_n")
+
+    def __init__(self, rec, x, n):
+        rec = np.array(rec, dtype=np.float64)
+        rec.setflags(write=False)
+        for name, value in (("_rec", rec), ("_x", x), ("_n", int(n))):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("BandInfo is read-only")
+
+    record = property(lambda self: self._rec)
+    status = property(lambda self: self.STATUS[int(self._rec[0])])
+    column = property(lambda self: int(self._rec[1]))
+    min_pivot = property(lambda self: float(self._rec[2]))
+    max_pivot = property(lambda self: float(self._rec[3]))
+    unknowns = property(lambda self: int(self._rec[4]))
+    width = property(lambda self: int(self._rec[5]))
+    border = property(lambda self: int(self._rec[6]))
+    interchanges = property(lambda self: int(self._rec[7]))
+    primal = property(lambda self: self._x[: self._n])
+    dual = property(lambda self: self._x[self._n:])
+
+    def __repr__(self):
+        return (f"BandInfo(status={self.status!r}, width={self.width}, border={self.border}, interchanges={self.interchanges}, "
+                f"min_pivot={self.min_pivot:.3e}, max_pivot={self.max_pivot:.3e})")
 
 
 class _Record:
@@ -1980,6 +2044,30 @@ class Linearization:
                                              runtime.as_dp(b), self._opt(x0), float(tol), int(2 * size if maxiter is None else maxiter),
                                              int(check_every), runtime.as_dp(x), runtime.as_dp(rec)))
         return x, MinresInfo(rec, tol, x, self.n)
+
+    def solve_banded(self, b, s1=None, s2=None):
+        """Solve ``K x = b`` (``kkt_v``'s matrix with the Hessian) by the bordered band LU on the device (csrc/pk_band.cpp):
+        the ordering is built from the CSR maps and the bounds' fixed variables (``pockit_amd.band.BandOrdering``; a
+        ``ValueError`` where the band is too wide), one call uploads ``b``, ``s1``, ``s2`` and downloads ``x`` and the record.
+        ``s1`` and ``s2``: a scalar, a vector or None (zeros).  Returns ``(x, info)``, ``info`` a ``BandInfo``; ``x`` is all
+        NaN unless ``info.status == "solved"``.  Fixed variables (``v_lb == v_ub``) are out of the system: their ``x`` is 0.0.
+        Pivoting never leaves the band part: a K whose band part is singular reports ``"singular_band_pivot"``."""
+        from .band import BandOrdering
+
+        ev, _, s1, s2 = self._kkt_args(s1, s2, True)
+        size = self.n + self.m
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (size,):
+            raise ValueError(f"b must have shape ({size},)")
+        s1 = np.zeros(self.n) if s1 is None else s1
+        s2 = np.zeros(self.m) if s2 is None else s2
+        free = np.asarray(ev.plan.v_lb, dtype=np.float64) != np.asarray(ev.plan.v_ub, dtype=np.float64)
+        ordering = BandOrdering(ev.csr_map("jac"), ev.csr_map("hess"), free)
+        ev.band_plan(ordering)
+        x, rec = np.full(size, np.nan), np.empty(8)
+        dp = runtime.as_dp
+        ev.ctx.check(ev.ctx.lib.pk_solve_banded(ev.ctx.handle, dp(s1), dp(s2), dp(b), dp(x), dp(rec)))
+        return x, BandInfo(rec, x, self.n)
 
     # ---- the dual side of optimality, and the first block of the KKT right-hand side (csrc/pk_ipm.cpp)
     def dual_residual(self, grad, lam, z=None, negate=False):

@@ -1,7 +1,8 @@
 """A primal-dual interior-point solver on the device-resident units of this package: ``solve(system, guess)`` needs no
 third-party optimiser.  The iterate -- x, the slacks s of the inequality rows, the multipliers lam of all rows and the bound
 multipliers of x and s -- stays in HBM; per iteration only records of a few doubles come down, plus, with
-``linear_solver="direct"``, the CSR values of J and H for a host sparse LU.
+``linear_solver="direct"``, the CSR values of J and H for a host sparse LU.  ``linear_solver="banded"``
+factors the step's system on the device instead: no matrix value crosses PCIe.
 
 The problem is ``min f(x)  s.t.  g_i(x) = c_i`` on equality rows (``c_lb == c_ub``), ``g_i(x) - s_i = 0`` with
 ``c_lb_i <= s_i <= c_ub_i`` on inequality rows, ``v_lb <= x <= v_ub``; a variable with ``v_lb == v_ub`` is fixed and out of the
@@ -12,7 +13,8 @@ system.  One iteration:
   ``slack_reduce_dev``: ``S2``, ``b2``, the infeasibility;
 * the step ``[[H + Sigma_x + delta_w, J^T], [J, -S2]] (dx, dlam) = (b1, b2)`` -- ``"direct"``: ``scipy.sparse.linalg.splu`` on the
   downloaded values, fixed variables' rows and columns dropped; ``"minres"``: ``minres_begin_dev`` / ``minres_advance_dev`` with
-  the diagonal preconditioner, fixed variables decoupled by a unit row (below);
+  the diagonal preconditioner, fixed variables decoupled by a unit row (below); ``"banded"``: ``band_factor_dev`` /
+  ``band_solve_dev``, a bordered band LU of the same matrix where its values lie (below);
 * ``slack_recover_dev``: ds and the inertia-free curvature test ``dx.(H + Sigma_x + delta_w) dx + ds.Sigma_s ds >= 1e-11 (|dx|^2 +
   |ds|^2)``, on failure ``delta_w`` grows (``Regularisation``);
 * ``ip_step_dev`` on x and on s: the multiplier steps and the fraction-to-the-boundary lengths;
@@ -31,7 +33,16 @@ barrier systems -- 700 to 3 400 iterations per step at ``rtol = 1e-8``, stopping
 because the preconditioned-norm test is met long before the step is accurate once Sigma spans eight decades; a loop driven by it
 stalled at 11 300 iterations per step; an interval-block Schur preconditioner cut the counts only 1.6-6x.  On pure-equality
 problems it works: lqr converged in 2-3 Newton iterations with 104 (6 x 6) and 332 (Radau 10 x 10) MINRES iterations.  Use it
-there; use ``"direct"`` otherwise."""
+there; use ``"direct"`` otherwise.
+
+``linear_solver="banded"``.  ``pockit_amd.band.BandOrdering`` orders K once per solve (the few dense unknowns -- a free final
+time -- to a border, reverse Cuthill-McKee on the rest) and ``band_plan`` uploads the plan; per attempt of the regularisation
+loop ``band_factor_dev`` assembles K from the resident CSR values with ``Sigma_x + delta_w`` and factors it, ``band_solve_dev``
+solves into the step, and the 64-byte record comes down.  A status other than 0 (a singular pivot, a non-finite column) is a
+failed attempt, as ``splu``'s ``RuntimeError`` is on the direct path.  No CSR value, ``Sigma_x``, ``S2`` or right-hand side is
+downloaded.  LIMIT: pivoting is confined to the band part.  A model whose band part (K without the border's rows and
+columns) is singular while K is not gets failed attempts here and should use ``"direct"``; so should a model whose
+half-bandwidth exceeds 192 or whose border exceeds 8 unknowns (``BandOrdering`` raises ``ValueError``)."""
 from __future__ import annotations
 
 import math
@@ -321,19 +332,25 @@ def _errors(q, m):
 def solve(system, guess, optimizer_options=None, *, linear_solver="direct"):
     """Solve the NLP of ``system`` from ``guess`` (the shapes of ``ipopt.solve``); returns ``(solution, info)``.  ``info`` has
     cyipopt's keys ``x, g, obj_val, mult_g, mult_x_L, mult_x_U, status, status_msg`` and ``iterations``, ``mu``, ``error`` (the
-    final E_0), ``linear_iterations`` (MINRES iterations in all; 0 on the direct path), ``regularisations``, and the slacks with
+    final E_0), ``linear_iterations`` (MINRES iterations in all; 0 on the direct and banded paths), ``regularisations``, and the slacks with
     their multipliers ``slack, mult_s_L, mult_s_U`` (m values; 0.0 on equality rows).  ``status``: 0 converged (``E_0 <= tol``),
     -1 maximum iterations, -2 no acceptable step, -13 a non-finite value.  Options: ``tol`` (1e-8), ``max_iter`` (200),
-    ``mu_init`` (0.1), ``print_level`` (0; 1 prints a line per iteration, 2 the step's figures as well, 3 every trial point).  ``linear_solver``: "direct" or "minres" (module
-    docstring: where the latter works)."""
-    if linear_solver not in ("direct", "minres"):
-        raise ValueError('linear_solver must be "direct" or "minres"')
+    ``mu_init`` (0.1), ``print_level`` (0; 1 prints a line per iteration, 2 the step's figures as well, 3 every trial point).  ``linear_solver``: "direct", "minres" or
+    "banded" (module docstring: where the latter two work); with "banded" a ``ValueError`` of the ordering (band too wide, border
+    too large) leaves the choice of "direct" to the caller."""
+    if linear_solver not in ("direct", "minres", "banded"):
+        raise ValueError('linear_solver must be "direct", "minres" or "banded"')
     opt = options(optimizer_options)
     x0, bare, _ = preprocess(system, guess, None)
     R = _Resident(system, x0)
     ev, at, torch, n, m = R.ev, R.at, R.torch, R.n, R.m
     tol, mu = opt["tol"], opt["mu_init"]
     direct = DirectKkt(R.map_j, R.map_h, R.free) if linear_solver == "direct" else None
+    banded = linear_solver == "banded"
+    if banded:
+        from ..band import BandOrdering
+
+        ev.band_plan(BandOrdering(R.map_j, R.map_h, R.free))
 
     # ---- the start: s = g(x) pushed inside the rows' bounds
     R.evaluate()
@@ -379,6 +396,13 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct"):
                     continue
                 R.sol = R.up(np.concatenate((dx, dlam)))
                 R.to_kernels()
+            elif banded:
+                R.to_kernels()
+                ev.band_factor_dev(at(R.ch), at(R.cj), at(R.s1), at(R.s2))
+                ev.band_solve_dev(at(R.rhs), at(R.sol))
+                br = ev.band_record()
+                if br[0] != 0.0 or not np.all(np.isfinite(br)):
+                    continue
             else:
                 k_s1 = R.s1 + R.fixed_s1
                 R.to_kernels()

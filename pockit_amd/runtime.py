@@ -150,6 +150,11 @@ PROTOTYPES = {
     "pk_slack_reduce": (C.c_int, [vp, dp, dp, dp, dp, dp, dp, dp, dp]),
     "pk_slack_recover": (C.c_int, [vp, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
     "pk_slack_update": (C.c_int, [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_double, C.c_double, dp]),
+    "pk_band_plan": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
+    "pk_band_factor_dev": (C.c_int, [vp, vp, vp, vp, vp]),
+    "pk_band_solve_dev": (C.c_int, [vp, vp, vp]),
+    "pk_band_record": (C.c_int, [vp, dp]),
+    "pk_solve_banded": (C.c_int, [vp, dp, dp, dp, dp, dp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -219,6 +224,8 @@ PROTOTYPES = {
                                 vp]),
     "pk_slack_raw_dev": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
                                    C.c_double, vp, vp]),
+    "pk_band_fill_dev": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "pk_band_raw_dev": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]),
 }
 EXPORTS = list(PROTOTYPES)
 

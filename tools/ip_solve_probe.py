@@ -3,6 +3,10 @@ and of one resident round of the interior-point iteration (everything but the li
 on downloaded vectors -- what a caller writes without the units.  Needs an MI355X; prints a table.
 
     python tools/ip_solve_probe.py [--runs 5] [--out profiles/ip_solve_probe_mi355x.txt] [--quadrotor]
+
+``--banded`` runs the rows of DESIGN.md section 23 instead: ``linear_solver="banded"`` alternating with ``"direct"`` on both
+sizes, and the host-landed time of one factorisation and of one solve of the band LU with their launches (``--append`` adds the
+rows to ``--out`` instead of replacing it).
 """
 import argparse
 import importlib
@@ -84,8 +88,70 @@ def numpy_round(R, J, H):
                 compl=max(out["x"]["compl"], out["s"]["compl"]), compl0=max(out["x"]["compl0"], out["s"]["compl0"]))
 
 
+def banded_rows(args, models, ipm):
+    """``"banded"`` alternating with ``"direct"``: whole solves, then one factorisation and one solve of the band LU at the
+    start point (enqueue and wait, host-landed), with the launches they take."""
+    from pockit_amd.band import BandOrdering
+
+    lines = [f"ip_solve_probe --banded: interior_point.solve, linear_solver \"banded\" alternating with \"direct\" (tol 1e-8); median [min, max] of "
+             f"{args.runs} runs each, host-landed (perf_counter around whole solves and around enqueue + wait)"]
+    for name, scheme, mesh, num_point in MODELS:
+        ns = importlib.import_module(f"pockit_amd.{scheme}")
+        system, _, guess = getattr(models, name)(ns, mesh, num_point)
+        times, infos = {"direct": [], "banded": []}, {}
+        ipm.solve(system, guess, linear_solver="banded")                    # warm-up: code objects, the batch's self-check
+        for _ in range(args.runs):
+            for solver in ("direct", "banded"):
+                t0 = time.perf_counter()
+                _, infos[solver] = ipm.solve(system, guess, linear_solver=solver)
+                times[solver].append(time.perf_counter() - t0)
+        lines.append(f"{name}({scheme}, {mesh}, {num_point}): n {system.plan.n}, m {system.plan.m}")
+        for solver in ("direct", "banded"):
+            info = infos[solver]
+            per = [t / max(1, info["iterations"]) for t in times[solver]]
+            lines.append(f"    {solver:7s} {spread(times[solver], 1e3)} ms per solve, {spread(per, 1e3, '9.2f')} ms per iteration; status {info['status']}, "
+                         f"{info['iterations']} Newton iterations, {info['regularisations']} regularised, f = {info['obj_val']:.10f}, E_0 {info['error']:.2e}")
+        R = ipm._Resident(system, ipm.preprocess(system, guess, None)[0])
+        R.evaluate()
+        R.to_torch()
+        t0 = time.perf_counter()
+        o = BandOrdering(R.map_j, R.map_h, R.free)
+        t_order = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        R.ev.band_plan(o)
+        t_plan = time.perf_counter() - t0
+        R.s1 = R.up(np.ones(R.n))
+        R.s2 = R.up(np.where(R.ineq, 1.0, 0.0))
+        R.rhs = R.up(np.random.default_rng(3).standard_normal(R.n + R.m))
+        R.to_kernels()
+        at, ev = R.at, R.ev
+        t_f, t_s = [], []
+        for _ in range(args.runs + 1):
+            t0 = time.perf_counter()
+            ev.band_factor_dev(at(R.ch), at(R.cj), at(R.s1), at(R.s2))
+            ev.sync()
+            t1 = time.perf_counter()
+            ev.band_solve_dev(at(R.rhs), at(R.sol))
+            ev.sync()
+            t2 = time.perf_counter()
+            t_f.append(t1 - t0)
+            t_s.append(t2 - t1)
+        rec = ev.band_record()
+        panels = -(-o.nb // 32)
+        lines.append(f"    ordering N {o.N}, Nb {o.nb}, w {o.w}, p {o.p}: {t_order * 1e3:.1f} ms on the host once per solve; plan upload ({8 * o.dests} bytes of map) "
+                     f"{t_plan * 1e3:.1f} ms")
+        lines.append(f"    factor  {spread(t_f[1:], 1e3, '9.3f')} ms: {2 + 2 * panels} launches at most (init, fill, {panels} panels with their updates), "
+                     f"{8 * o.dests} bytes of [band | U | C] written; status {int(rec[0])}, {int(rec[7])} interchanges, pivots [{rec[2]:.2e}, {rec[3]:.2e}]")
+        lines.append(f"    solve   {spread(t_s[1:], 1e3, '9.3f')} ms: {6 if o.p else 3} launches (right-hand sides, sweeps"
+                     f"{', dots, border, x_B' if o.p else ''}, scatter), {o.p + 1} right-hand side{'s' if o.p else ''} of {o.nb} in one workgroup each")
+        system.evaluator.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--banded", action="store_true", help="the rows of the banded step solver instead (DESIGN.md section 23)")
+    ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--quadrotor", action="store_true", help="also run planar_quadrotor(radau, 14, 6) once and report what happens")
@@ -96,6 +162,13 @@ def main():
     from pockit_amd.optimizer import interior_point as ipm
     from pockit_amd.optimizer import scipy as scipy_solver
 
+    if args.banded:
+        text = "\n".join(banded_rows(args, models, ipm)) + "\n"
+        print(text, end="")
+        if args.out:
+            with open(args.out, "a" if args.append else "w") as fh:
+                fh.write(text)
+        return
     lines = [f"ip_solve_probe: interior_point.solve (direct, tol 1e-8) against optimizer.scipy.solve (trust-constr, gtol 1e-9, xtol 1e-11); "
              f"median [min, max] of {args.runs} alternating runs, host-landed (perf_counter around whole solves and around rounds that end in a wait)"]
     for name, scheme, mesh, num_point in MODELS:
