@@ -539,6 +539,30 @@ int pk_band_solve_dev(pk_ctx* ctx, const double* d_rhs, double* d_sol);
 int pk_band_record(pk_ctx* ctx, double* rec /* 8 */);
 int pk_solve_banded(pk_ctx* ctx, const double* s1, const double* s2, const double* b, double* x, double* rec /* 8 */);
 
+/* A BATCH OF STEP SYSTEMS BEHIND ONE PLAN (kernels pk_bd_init_bk ... pk_bd_scatter_bk: the same bodies, the entry from the grid's
+ * second dimension).  B systems, 1 <= B <= 16, share pk_band_plan's ordering, w, p and assembly map; each
+ * has its own values.  Entry e is assembled, factored and solved exactly as the single forms do it: its solution and its record
+ * are, bit for bit, those of pk_band_factor_dev / pk_band_solve_dev on entry e's inputs alone.  A batch costs the launches of one
+ * system, each with B times the workgroups.  Strides are in doubles: entry e of an array begins e strides behind entry 0.  A source
+ * stride of 0 means that all entries read the same array; otherwise it is at least the array's length (hvals and jvals: the CSR
+ * value counts, s1: n, s2: m, rhs and sol: n + m).  An entry that fails (status != 0) does not stop the others: its slice of sol
+ * is left untouched, theirs are complete.  The batch has its own arrays, reserved by the first call and grown by a larger B: a
+ * batch call leaves the factors of pk_band_factor_dev in place and the other way round; a new plan invalidates both.
+ * pk_band_solve_batch_dev and pk_band_record_batch take the B of the last pk_band_factor_batch_dev; the record of entry e is at
+ * rec + 8 e.  pk_solve_banded_batch is the host form on pk_linearize's values (J and H shared by the entries): one upload of
+ * b, s1, s2 (B rows each), one download of x and the records; the rows of x whose entry failed are left as the caller gave them.
+ * Errors: 134 B outside 1 ... 16, a stride that is neither 0 nor at least the length, an output stride below the length, no
+ * plan, CSR maps changed since the plan, a solve or a record without a batch factorisation of that B; 110 a null device pointer;
+ * 60 a null host buffer; 119 a sharded context; 136 no device memory (the message names the array and B); the host form also 117
+ * and 118 as pk_solve_banded.  Nothing is enqueued or written after a refusal. */
+int pk_band_factor_batch_dev(pk_ctx* ctx, int32_t B, const double* d_hvals, int64_t stride_h, const double* d_jvals, int64_t stride_j,
+                             const double* d_s1, int64_t stride_s1, const double* d_s2, int64_t stride_s2);
+int pk_band_solve_batch_dev(pk_ctx* ctx, int32_t B, const double* d_rhs, int64_t stride_rhs /* 0 or >= n + m */, double* d_sol,
+                            int64_t stride_sol /* >= n + m */);
+int pk_band_record_batch(pk_ctx* ctx, int32_t B, double* rec /* 8 B: entry e at rec + 8 e */);
+int pk_solve_banded_batch(pk_ctx* ctx, int32_t B, const double* s1 /* B x n */, const double* s2 /* B x m */,
+                          const double* b /* B x (n + m) */, double* x /* B x (n + m) */, double* rec /* 8 B */);
+
 #ifdef __cplusplus
 }
 #endif

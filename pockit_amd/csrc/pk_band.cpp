@@ -77,6 +77,15 @@ struct PkBandArgs {
   int32_t w, p, planes;
 };
 
+// A batch: B <= PK_BD_BATCH_CAP systems behind ONE plan (shape, map, order, where and j0 are shared).  `a` holds entry 0; entry
+// e's arrays begin e strides behind it, in elements of each array.  A stride of 0 (sources only) makes every entry read the same
+// array.  Y, x and b_C are slices of one work array per entry and move together.  No entry reads or writes another's slices.
+enum { PK_BD_BATCH_CAP = 16 };
+struct PkBandBatchArgs {
+  PkBandArgs a;
+  int64_t s_h, s_j, s_s1, s_s2, s_band, s_U, s_C, s_ipiv, s_work, s_rec, s_partial, s_rhs, s_sol;
+};
+
 #ifdef __HIPCC__
 #define BD_BODY __device__ __forceinline__
 #define BD_PHASE(call)                    \
@@ -105,6 +114,19 @@ PK_LIB_FN double* bd_at(const PkBandArgs& a, int64_t i, int64_t j) { return a.ba
 // touched yet -- read as 0.0 whatever the memory holds: the kernels never read the fill rows a caller hands over
 PK_LIB_FN bool bd_stored(const PkBandArgs& a, int64_t i, int64_t j) { return i - j <= a.w && j - i <= 2 * (int64_t)a.w; }
 PK_LIB_FN bool bd_fresh(const PkBandArgs& a, int64_t i, int64_t j) { return j - i > a.w && (a.j0 == 0 || j >= a.j0 + 2 * (int64_t)a.w); }
+
+// the arguments of entry e of a batch: every pointer moved by the entry's stride (an array the form does not use is null and
+// its stride 0), everything else as it is
+PK_LIB_FN PkBandArgs bd_entry(const PkBandBatchArgs& g, int64_t e) {
+  PkBandArgs a = g.a;
+  a.hvals += e * g.s_h; a.jvals += e * g.s_j; a.s1 += e * g.s_s1; a.s2 += e * g.s_s2;
+  a.band += e * g.s_band; a.U += e * g.s_U; a.C += e * g.s_C;
+  a.ipiv += e * g.s_ipiv;
+  a.Y += e * g.s_work; a.x += e * g.s_work; a.bc += e * g.s_work;
+  a.rec += e * g.s_rec; a.partial += e * g.s_partial;
+  a.rhs += e * g.s_rhs; a.sol += e * g.s_sol;
+  return a;
+}
 
 // ---------------------------------------------------------------- elementwise work
 PK_LIB_FN void bd_init_thread(const PkBandArgs& a, int t) {
@@ -519,6 +541,100 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_bd_scatter_k(PkBandArgs a) {
     hipLaunchKernelGGL(pk_bd_update_k, dim3(grid), dim3(PK_BLOCK), 0, (st), (a), (columns));        \
     PK_HIP((c), hipGetLastError());                                                                 \
   } while (0)
+
+// ---------------------------------------------------------------- the batch kernels: grid (the single kernel's, B)
+// Entry blockIdx.y's arguments, then the single kernel's walk of blockIdx.x over the same body with the same static LDS.
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_init_bk(PkBandBatchArgs g) {
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  bd_init_thread(a, (int)threadIdx.x);
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_fill_bk(PkBandBatchArgs g) {
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  const int64_t items = bd_items(a.dests);
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t d = item * PK_BLOCK + (int64_t)threadIdx.x;
+    if (d < a.dests) bd_fill_element(a, d);
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_panel_bk(PkBandBatchArgs g) {
+  __shared__ double T[BD_LD * PK_BD_NB];
+  __shared__ double s[2 * PK_BLOCK];
+  __shared__ int piv[PK_BD_NB];
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  bd_panel_body(a, T, s, piv);
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_update_bk(PkBandBatchArgs g, int64_t columns) {
+  __shared__ double col[PK_BLOCK];
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  for (int64_t item = (int64_t)blockIdx.x; item < columns; item += (int64_t)gridDim.x) bd_update_body(a, item, col);
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_prep_bk(PkBandBatchArgs g) {
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  const int64_t len = a.nb * (a.p + 1) + a.p, items = bd_items(len);
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
+    if (e < len) bd_prep_element(a, e);
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_solve_bk(PkBandBatchArgs g) {
+  __shared__ double F[PK_BD_CH * BD_LW];
+  __shared__ double ring[PK_BD_RING];
+  __shared__ int ipl[PK_BD_CH];
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  for (int64_t q = (int64_t)blockIdx.x; q <= a.p; q += (int64_t)gridDim.x) bd_solve_body(a, q, F, ring, ipl);
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_dot_bk(PkBandBatchArgs g) {
+  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  const int t = (int)threadIdx.x;
+  const int64_t items = (a.p + 1) * a.n_pieces;
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t r = item / a.n_pieces, pc = item % a.n_pieces;
+    bd_dot_thread(a, r, pc, t, s);
+    __syncthreads();
+    lib_tree(lib_planes_step, s, t, (int)a.p);
+    if (t < a.p) bd_dot_store(a, r, pc, t, s);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_border_bk(PkBandBatchArgs g) {
+  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
+  __shared__ double dots[(PK_BD_P_CAP + 1) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], v[PK_BD_P_CAP];
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  bd_border_body(a, s, dots, S, v);
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_xb_bk(PkBandBatchArgs g) {
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  if (a.rec[BD_STATUS] != 0.0) return;
+  const int64_t items = bd_items(a.nb);
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t i = item * PK_BLOCK + (int64_t)threadIdx.x;
+    if (i < a.nb) bd_xb_element(a, i);
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_scatter_bk(PkBandBatchArgs g) {
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  if (a.rec[BD_STATUS] != 0.0) return;
+  const int64_t items = bd_items(a.nsol);
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t i = item * PK_BLOCK + (int64_t)threadIdx.x;
+    if (i < a.nsol) bd_scatter_element(a, i);
+  }
+}
+#define BD_LAUNCH_UPDATE_Y(c, grid, ny, st, g, columns)                                                      \
+  do {                                                                                                       \
+    hipLaunchKernelGGL(pk_bd_update_bk, dim3((grid), (ny)), dim3(PK_BLOCK), 0, (st), (g), (columns));        \
+    PK_HIP((c), hipGetLastError());                                                                          \
+  } while (0)
 #else
 // ---------------------------------------------------------------- host stand-in: the identical walk
 static void bd_init_host(const PkBandArgs& a, unsigned) { bd_init_thread(a, 0); }
@@ -568,12 +684,28 @@ static void bd_scatter_host(const PkBandArgs& a, unsigned grid) {
 }
 #define BD_LAUNCH_UPDATE(c, grid, st, a, columns) \
   fake_hip_enqueue((st), [a_ = (a), g_ = (grid), n_ = (columns)]() { bd_update_host(a_, g_, n_); })
+
+// the batch kernels' stand-ins: entry y's arguments, then the single form's walk (PK_LIB_LAUNCH_Y walks the entries outermost)
+static void bd_init_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_init_host(bd_entry(g, y), grid); }
+static void bd_fill_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_fill_host(bd_entry(g, y), grid); }
+static void bd_panel_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_panel_host(bd_entry(g, y), grid); }
+static void bd_prep_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_prep_host(bd_entry(g, y), grid); }
+static void bd_solve_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_solve_host(bd_entry(g, y), grid); }
+static void bd_dot_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_dot_host(bd_entry(g, y), grid); }
+static void bd_border_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_border_host(bd_entry(g, y), grid); }
+static void bd_xb_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_xb_host(bd_entry(g, y), grid); }
+static void bd_scatter_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_scatter_host(bd_entry(g, y), grid); }
+#define BD_LAUNCH_UPDATE_Y(c, grid, ny, st, g, columns)                                                \
+  fake_hip_enqueue((st), [a_ = (g), g_ = (grid), y_ = (unsigned)(ny), n_ = (columns)]() {              \
+    for (unsigned y = 0; y < y_; ++y) bd_update_host(bd_entry(a_, y), g_, n_);                         \
+  })
 #endif
 
 void free_band(pk_ctx* c) {
   PkBand& b = c->band;
   release(b.d_map); release(b.d_order); release(b.d_where);
   release(b.d_work); release(b.d_ipiv); release(b.d_partial); release(b.d_scratch); release(b.d_raw);
+  release(b.d_bwork); release(b.d_bipiv); release(b.d_bpartial); release(b.d_bscratch); release(b.d_braw);
   b = PkBand{};
 }
 
@@ -658,6 +790,99 @@ PkBandArgs bd_planned(pk_ctx* c) {
   a.nh = c->csr[1].n_unique; a.nj = c->csr[0].n_unique; a.ns1 = c->n;
   a.nsol = (int64_t)c->n + c->m;
   return a;
+}
+
+// ---------------------------------------------------------------- the batch: the same launch sequences with the grid (., B)
+int bd_enqueue_factor_batch(pk_ctx* c, PkBandBatchArgs g, int32_t B, bool fill, hipStream_t st) {
+  const PkBandArgs& a = g.a;
+  PK_LIB_LAUNCH_Y(c, pk_bd_init_bk, bd_init_bhost, 1u, B, st, g);
+  if (fill && a.dests > 0) PK_LIB_LAUNCH_Y(c, pk_bd_fill_bk, bd_fill_bhost, lib_grid(lib_elem_items(a.dests)), B, st, g);
+  for (int64_t j0 = 0; j0 < a.nb; j0 += PK_BD_NB) {
+    g.a.j0 = j0;
+    PK_LIB_LAUNCH_Y(c, pk_bd_panel_bk, bd_panel_bhost, 1u, B, st, g);
+    const int64_t j1 = std::min<int64_t>(j0 + PK_BD_NB, a.nb);
+    const int64_t columns = std::min<int64_t>(j1 - 1 + 2 * (int64_t)a.w, a.nb - 1) - j1 + 1;
+    if (columns > 0) BD_LAUNCH_UPDATE_Y(c, lib_grid(columns), B, st, g, columns);
+  }
+  return 0;
+}
+
+int bd_enqueue_solve_batch(pk_ctx* c, PkBandBatchArgs g, int32_t B, hipStream_t st) {
+  const PkBandArgs& a = g.a;
+  if (a.nb + a.p > 0) PK_LIB_LAUNCH_Y(c, pk_bd_prep_bk, bd_prep_bhost, lib_grid(lib_elem_items(a.nb * (a.p + 1) + a.p)), B, st, g);
+  if (a.nb > 0) PK_LIB_LAUNCH_Y(c, pk_bd_solve_bk, bd_solve_bhost, lib_grid((int64_t)a.p + 1), B, st, g);
+  double* from = a.Y;      // (without a border the solution is y_b itself; Y and x move by the same stride)
+  if (a.p > 0) {
+    PK_LIB_LAUNCH_Y(c, pk_bd_dot_bk, bd_dot_bhost, lib_grid((a.p + 1) * a.n_pieces), B, st, g);
+    PK_LIB_LAUNCH_Y(c, pk_bd_border_bk, bd_border_bhost, 1u, B, st, g);
+    if (a.nb > 0) PK_LIB_LAUNCH_Y(c, pk_bd_xb_bk, bd_xb_bhost, lib_grid(lib_elem_items(a.nb)), B, st, g);
+    from = a.x;
+  }
+  g.a.x = from;
+  if (a.nsol > 0) PK_LIB_LAUNCH_Y(c, pk_bd_scatter_bk, bd_scatter_bhost, lib_grid(lib_elem_items(a.nsol)), B, st, g);
+  return 0;
+}
+
+int bd_batch_size(pk_ctx* c, int32_t B, const char* who) {
+  if (B < 1 || B > PK_BD_BATCH_CAP) return fail(c, 134, "%s: a batch of %d (1 ... %d)", who, B, (int)PK_BD_BATCH_CAP);
+  return 0;
+}
+
+// a source may be shared (stride 0) or its entries lie at least a length apart; an output's entries always do
+int bd_stride(pk_ctx* c, int64_t stride, int64_t len, bool source, const char* who, const char* what) {
+  if ((source && stride == 0) || stride >= std::max<int64_t>(len, source ? 1 : 0)) return 0;
+  return fail(c, 134, "%s: a stride of %lld doubles for %s of %lld (%sat least the length)", who, (long long)stride, what, (long long)len,
+              source ? "0, or " : "");
+}
+
+// an array of the batch for B entries; what it was reserved for goes into the message
+int bd_batch_reserve(pk_ctx* c, double*& p, size_t& cap, size_t per, int32_t B, bool factors, const char* who, const char* what) {
+  if (per * (size_t)B <= cap) return 0;
+  char named[160];
+  std::snprintf(named, sizeof named, "%s of a batch of %d (%zu doubles each)", what, (int)B, per);
+  const int rc = lib_reserve(c, p, cap, per * (size_t)B, 136, who, named);
+  if (!rc && factors) c->band.batch = 0;      // (the array that went held the last batch factorisation)
+  return rc;
+}
+
+// doubles of one entry of the planned batch, [band | U | C | Y | x | b_C]; the B records lie behind the B entries
+size_t bd_entry_doubles(int64_t nb, int64_t w, int64_t p) { return bd_matrix_doubles(nb, w, p) + bd_solve_doubles(nb, p) - PK_BD_REC; }
+size_t bd_ipiv_doubles(int64_t nb) { return (size_t)nb / 2 + 1; }
+
+// the arguments of B planned systems in the batch's arrays (reserved for at least B)
+PkBandBatchArgs bd_planned_batch(pk_ctx* c, int32_t B) {
+  const PkBand& b = c->band;
+  PkBandBatchArgs g{};
+  PkBandArgs& a = g.a;
+  a = bd_planned(c);
+  const int64_t per = (int64_t)bd_entry_doubles(b.nb, b.w, b.p);
+  a.band = b.d_bwork; a.U = a.band + a.ldab * a.nb; a.C = a.U + a.nb * a.p;
+  bd_solve_slices(a, b.d_bwork + a.dests);
+  a.rec = b.d_bwork + per * B;
+  a.ipiv = (int32_t*)b.d_bipiv;
+  g.s_band = g.s_U = g.s_C = g.s_work = per;
+  g.s_rec = PK_BD_REC;
+  g.s_ipiv = 2 * (int64_t)bd_ipiv_doubles(b.nb);
+  return g;
+}
+
+int bd_partial_batch(pk_ctx* c, PkBandBatchArgs& g, int32_t B, const char* who) {
+  PkBandArgs& a = g.a;
+  a.n_pieces = lib_dot_pieces(a.nb);
+  const size_t per = (size_t)(a.p + 1) * (size_t)a.p * (size_t)a.n_pieces;
+  if (a.p > 0) {
+    if (const int rc = bd_batch_reserve(c, c->band.d_bpartial, c->band.bpartial_cap, per, B, false, who, "the partial sums")) return rc;
+  }
+  a.partial = a.p > 0 ? c->band.d_bpartial : nullptr;
+  g.s_partial = a.p > 0 ? (int64_t)per : 0;
+  return 0;
+}
+
+int bd_batch_planned(pk_ctx* c, const char* who) {
+  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
+  if (c->band.sources != c->csr[1].n_unique + c->csr[0].n_unique + (int64_t)c->n + c->m)
+    return fail(c, 134, "%s: the CSR maps changed since pk_band_plan", who);
+  return 0;
 }
 
 }  // namespace
@@ -774,6 +999,91 @@ int pk_solve_banded(pk_ctx* c, const double* s1, const double* s2, const double*
   return 0;
 }
 
+int pk_band_factor_batch_dev(pk_ctx* c, int32_t B, const double* d_hvals, int64_t stride_h, const double* d_jvals, int64_t stride_j,
+                             const double* d_s1, int64_t stride_s1, const double* d_s2, int64_t stride_s2) {
+  const char* who = "pk_band_factor_batch";
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!d_hvals || !d_jvals || !d_s1 || !d_s2) return fail(c, 110, "%s: null device pointer", who);
+  if ((rc = bd_context(c, who)) || (rc = bd_batch_size(c, B, who)) || (rc = bd_batch_planned(c, who))) return rc;
+  if ((rc = bd_stride(c, stride_h, c->csr[1].n_unique, true, who, "the Hessian's values")) ||
+      (rc = bd_stride(c, stride_j, c->csr[0].n_unique, true, who, "the Jacobian's values")) ||
+      (rc = bd_stride(c, stride_s1, c->n, true, who, "s1")) || (rc = bd_stride(c, stride_s2, c->m, true, who, "s2")))
+    return rc;
+  PkBand& b = c->band;
+  if ((rc = bd_batch_reserve(c, b.d_bwork, b.bwork_cap, bd_entry_doubles(b.nb, b.w, b.p) + PK_BD_REC, B, true, who,
+                             "the bands, the borders and the right-hand sides")) ||
+      (rc = bd_batch_reserve(c, b.d_bipiv, b.bipiv_cap, bd_ipiv_doubles(b.nb), B, true, who, "the interchanges")))
+    return rc;
+  PkBandBatchArgs g = bd_planned_batch(c, B);
+  g.a.hvals = d_hvals; g.a.jvals = d_jvals; g.a.s1 = d_s1; g.a.s2 = d_s2;
+  g.s_h = stride_h; g.s_j = stride_j; g.s_s1 = stride_s1; g.s_s2 = stride_s2;
+  b.batch = 0;      // (the factors of an earlier batch are overwritten from here on)
+  if ((rc = bd_enqueue_factor_batch(c, g, B, true, c->stream))) return rc;
+  b.batch = B;
+  return 0;
+}
+
+int pk_band_solve_batch_dev(pk_ctx* c, int32_t B, const double* d_rhs, int64_t stride_rhs, double* d_sol, int64_t stride_sol) {
+  const char* who = "pk_band_solve_batch";
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!d_rhs || !d_sol) return fail(c, 110, "%s: null device pointer", who);
+  if ((rc = bd_context(c, who)) || (rc = bd_batch_size(c, B, who))) return rc;
+  if (!c->band.planned || c->band.batch != B)
+    return fail(c, 134, "%s: no batch factorisation of %d entries (pk_band_plan, pk_band_factor_batch_dev; the last one had %d)", who, B,
+                (int)c->band.batch);
+  const int64_t N = (int64_t)c->n + c->m;
+  if ((rc = bd_stride(c, stride_rhs, N, true, who, "the right-hand sides")) || (rc = bd_stride(c, stride_sol, N, false, who, "the solutions")))
+    return rc;
+  PkBandBatchArgs g = bd_planned_batch(c, B);
+  if ((rc = bd_partial_batch(c, g, B, who))) return rc;
+  g.a.rhs = d_rhs; g.a.sol = d_sol;
+  g.s_rhs = stride_rhs; g.s_sol = stride_sol;
+  return bd_enqueue_solve_batch(c, g, B, c->stream);
+}
+
+int pk_band_record_batch(pk_ctx* c, int32_t B, double* rec) {
+  const char* who = "pk_band_record_batch";
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!rec) return fail(c, 60, "null host buffer");
+  if ((rc = bd_batch_size(c, B, who))) return rc;
+  if (!c->band.planned || c->band.batch != B)
+    return fail(c, 134, "%s: no batch factorisation of %d entries (pk_band_plan, pk_band_factor_batch_dev; the last one had %d)", who, B,
+                (int)c->band.batch);
+  const PkBandBatchArgs g = bd_planned_batch(c, B);
+  PK_HIP(c, hipSetDevice(c->device));
+  PK_HIP(c, hipMemcpyAsync(rec, g.a.rec, sizeof(double) * PK_BD_REC * (size_t)B, hipMemcpyDeviceToHost, c->stream));      // (the records are one array)
+  PK_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int pk_solve_banded_batch(pk_ctx* c, int32_t B, const double* s1, const double* s2, const double* b, double* x, double* rec) {
+  const char* who = "pk_solve_banded_batch";
+  const double *jvals = nullptr, *hvals = nullptr;
+  int rc = host_ready(c, s1 && s2 && b && x && rec);
+  if (rc || (rc = solve_ops_ready(c, true, true, who))) return rc;
+  if ((rc = bd_context(c, who)) || (rc = bd_batch_size(c, B, who))) return rc;
+  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
+  if ((rc = solve_linearized(c, true, jvals, hvals, who))) return rc;
+  const size_t n = (size_t)c->n, m = (size_t)c->m, N = n + m, nB = (size_t)B;
+  if ((rc = lib_reserve(c, c->band.d_bscratch, c->band.bscratch_cap, 3 * N * nB + 1, 136, who, "host-form scratch of the batch"))) return rc;
+  double *d_b = c->band.d_bscratch, *d_s1 = d_b + N * nB, *d_s2 = d_s1 + n * nB, *d_x = d_s2 + m * nB;
+  PK_HIP(c, hipSetDevice(c->device));
+  if ((rc = lib_upload(c, d_b, b, N * nB)) || (rc = lib_upload(c, d_s1, s1, n * nB)) || (rc = lib_upload(c, d_s2, s2, m * nB))) return rc;
+  // (an array of length 0 has nothing to tell apart: its stride is 0)
+  if ((rc = pk_band_factor_batch_dev(c, B, hvals, 0, jvals, 0, d_s1, (int64_t)n, d_s2, (int64_t)m)) ||
+      (rc = pk_band_solve_batch_dev(c, B, d_b, (int64_t)N, d_x, (int64_t)N)))
+    return rc;
+  std::vector<double> got(N * nB + 1);
+  if (N) PK_HIP(c, hipMemcpyAsync(got.data(), d_x, sizeof(double) * N * nB, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = pk_band_record_batch(c, B, rec))) return rc;      // (synchronises)
+  for (size_t e = 0; e < nB; ++e)
+    if (rec[PK_BD_REC * e + BD_STATUS] == 0.0) std::copy(got.begin() + (long)(N * e), got.begin() + (long)(N * (e + 1)), x + N * e);
+  return 0;
+}
+
 int pk_band_fill_dev(pk_ctx* c, const double* d_hvals, const double* d_jvals, const double* d_s1, const double* d_s2, double* d_out) {
   const char* who = "pk_band_fill";
   int rc = ready(c);
@@ -807,6 +1117,36 @@ int pk_band_raw_dev(pk_ctx* c, int64_t nb, int32_t w, int32_t p, int32_t R, doub
   bd_solve_slices(a, c->band.d_raw);
   if ((rc = bd_enqueue_factor(c, a, false, c->stream))) return rc;
   return bd_enqueue_solve(c, a, c->stream);
+}
+
+int pk_band_raw_batch_dev(pk_ctx* c, int32_t B, int64_t nb, int32_t w, int32_t p, int32_t R, double* d_band, int64_t stride_band,
+                          const double* d_U, int64_t stride_U, const double* d_C, int64_t stride_C, const double* d_rhs, int64_t stride_rhs,
+                          int32_t* d_ipiv, int64_t stride_ipiv, double* d_x, int64_t stride_x, double* d_rec, int64_t stride_rec) {
+  const char* who = "pk_band_raw_batch";
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!d_band || !d_rhs || !d_ipiv || !d_x || !d_rec || (p > 0 && (!d_U || !d_C))) return fail(c, 110, "%s: null device pointer", who);
+  if ((rc = bd_batch_size(c, B, who)) || (rc = bd_shape(c, nb, w, p, who))) return rc;
+  if (R != p + 1) return fail(c, 134, "%s: R = %d right-hand sides for a border of %d (p + 1: the border's columns and b)", who, R, p);
+  if ((rc = bd_stride(c, stride_band, bd_ldab(w) * nb, false, who, "the bands")) || (rc = bd_stride(c, stride_U, nb * p, true, who, "U")) ||
+      (rc = bd_stride(c, stride_C, (int64_t)p * p, true, who, "C")) || (rc = bd_stride(c, stride_rhs, nb + p, true, who, "the right-hand sides")) ||
+      (rc = bd_stride(c, stride_ipiv, nb, false, who, "the interchanges")) || (rc = bd_stride(c, stride_x, nb + p, false, who, "the solutions")) ||
+      (rc = bd_stride(c, stride_rec, PK_BD_REC, false, who, "the records")))
+    return rc;
+  PkBandBatchArgs g{};
+  PkBandArgs& a = g.a;
+  a.nb = nb; a.w = w; a.p = p; a.ldab = bd_ldab(w);
+  a.band = d_band; a.U = const_cast<double*>(d_U); a.C = const_cast<double*>(d_C);      // (no fill: the kernels read them only)
+  a.ipiv = d_ipiv; a.rec = d_rec; a.rhs = d_rhs; a.sol = d_x; a.nsol = nb + p;
+  g.s_band = stride_band; g.s_U = d_U ? stride_U : 0; g.s_C = d_C ? stride_C : 0; g.s_rhs = stride_rhs;
+  g.s_ipiv = stride_ipiv; g.s_sol = stride_x; g.s_rec = stride_rec;
+  g.s_work = (int64_t)bd_solve_doubles(nb, p);
+  if ((rc = bd_batch_reserve(c, c->band.d_braw, c->band.braw_cap, (size_t)g.s_work, B, false, who, "the right-hand sides")) ||
+      (rc = bd_partial_batch(c, g, B, who)))
+    return rc;
+  bd_solve_slices(a, c->band.d_braw);
+  if ((rc = bd_enqueue_factor_batch(c, g, B, false, c->stream))) return rc;
+  return bd_enqueue_solve_batch(c, g, B, c->stream);
 }
 
 }  // extern "C"

@@ -47,6 +47,13 @@ __device__ __forceinline__ void lib_tree(Step step, double* s, int t, More... mo
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(PK_BLOCK), 0, (st), (args));     \
     PK_HIP((c), hipGetLastError());                                              \
   } while (0)
+// The second form, for a batch of systems behind one plan: the grid is (grid, ny); the kernel takes its entry from blockIdx.y
+// and walks blockIdx.x as under the one-dimensional form.
+#define PK_LIB_LAUNCH_Y(c, kernel, host_walk, grid, ny, st, args)                       \
+  do {                                                                                  \
+    hipLaunchKernelGGL(kernel, dim3((grid), (ny)), dim3(PK_BLOCK), 0, (st), (args));    \
+    PK_HIP((c), hipGetLastError());                                                     \
+  } while (0)
 #else
 template <class Step, class... More>
 inline void lib_tree_host(Step step, double* s, More... more) {
@@ -63,6 +70,11 @@ inline void lib_walk_host(unsigned grid, int64_t items, Item item) {
 
 #define PK_LIB_LAUNCH(c, kernel, host_walk, grid, st, args) \
   fake_hip_enqueue((st), [a_ = (args), g_ = (grid)]() { host_walk(a_, g_); })
+// the second form: the entries outermost; host_walk(args, grid, y) is the one-dimensional walk of entry y
+#define PK_LIB_LAUNCH_Y(c, kernel, host_walk, grid, ny, st, args)                \
+  fake_hip_enqueue((st), [a_ = (args), g_ = (grid), y_ = (unsigned)(ny)]() {     \
+    for (unsigned y = 0; y < y_; ++y) host_walk(a_, g_, y);                      \
+  })
 #endif
 
 // ---------------------------------------------------------------- the pieced dot of pk_cg.cpp and pk_minres.cpp

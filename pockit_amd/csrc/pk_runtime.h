@@ -241,6 +241,19 @@ struct PkBand {
   int64_t nb = 0, w = 0, p = 0;
   int64_t sources = 0;              // entries of [hvals | jvals | s1 | s2] the plan was checked against
   bool planned = false, factored = false;
+  // the batch forms (pk_band_factor_batch_dev ...): B systems behind the one plan, reserved by the first batch call, grown by a
+  // larger B, released with the plan
+  double* d_bwork = nullptr;        // B x [band | U | C | Y | x | b_C], then the B records of 8
+  size_t bwork_cap = 0;
+  double* d_bipiv = nullptr;        // B x the interchanges
+  size_t bipiv_cap = 0;
+  double* d_bpartial = nullptr;     // B x the partial sums of the border's dots
+  size_t bpartial_cap = 0;
+  double* d_bscratch = nullptr;     // the host batch form's [b | s1 | s2 | x], B of each
+  size_t bscratch_cap = 0;
+  double* d_braw = nullptr;         // pk_band_raw_batch_dev's B x [Y | x | b_C]
+  size_t braw_cap = 0;
+  int32_t batch = 0;                // the entries of the last batch factorisation (0: none)
 };
 
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)

@@ -256,6 +256,13 @@ int pk_slack_raw_dev(pk_ctx* ctx, int kind, int64_t n, int64_t m, int64_t batch,
 int pk_band_fill_dev(pk_ctx* ctx, const double* d_hvals, const double* d_jvals, const double* d_s1, const double* d_s2, double* d_out);
 int pk_band_raw_dev(pk_ctx* ctx, int64_t nb, int32_t w, int32_t p, int32_t R, double* d_band, const double* d_U, const double* d_C,
                     const double* d_rhs, int32_t* d_ipiv, double* d_x, double* d_rec);
+/* The batch of pk_band_raw_dev: B systems of one shape (1 <= B <= 16), entry e of every array e strides behind entry 0 (strides
+ * in elements of the array; 0 allowed for d_U, d_C and d_rhs, which are only read: all entries share the array; every other
+ * stride at least the array's length).  No fill happens.  Entry e gets the bits pk_band_raw_dev gives for its arrays alone; a
+ * failed entry does not stop the others.  Errors 110, 134, 136. */
+int pk_band_raw_batch_dev(pk_ctx* ctx, int32_t B, int64_t nb, int32_t w, int32_t p, int32_t R, double* d_band, int64_t stride_band,
+                          const double* d_U, int64_t stride_U, const double* d_C, int64_t stride_C, const double* d_rhs, int64_t stride_rhs,
+                          int32_t* d_ipiv, int64_t stride_ipiv, double* d_x, int64_t stride_x, double* d_rec, int64_t stride_rec);
 
 #ifdef __cplusplus
 }

@@ -1420,6 +1420,31 @@ class Evaluator:
         self.ctx.check(self.ctx.lib.pk_band_record(self.ctx.handle, runtime.as_dp(rec)))
         return rec
 
+    def band_factor_batch_dev(self, B, d_hvals, d_jvals, d_s1, d_s2, strides=None):
+        """Enqueue ``band_factor_dev`` for B systems (1 ... 16) behind the one plan in one launch sequence: entry e reads its
+        arrays e strides behind the pointers.  ``strides``: the doubles between two entries of ``(hvals, jvals, s1, s2)``,
+        0 for an array all entries share (otherwise at least its length); None: ``(0, 0, n, 0)``, one H, J and ``s2`` under B
+        different ``s1``.  Every entry gets the bits ``band_factor_dev`` gives for its inputs alone.  The batch has its own
+        arrays: the factors of ``band_factor_dev`` stay.  Not waited for."""
+        sh, sj, s1, s2 = (0, 0, self.plan.n, 0) if strides is None else strides
+        self.ctx.check(self.ctx.lib.pk_band_factor_batch_dev(self.ctx.handle, int(B), d_hvals, int(sh), d_jvals, int(sj), d_s1, int(s1), d_s2,
+                                                             int(s2)))
+
+    def band_solve_batch_dev(self, B, d_rhs, d_sol, stride_rhs=0, stride_sol=None):
+        """Enqueue the B solves ``K_e sol_e = rhs_e`` with the factors of ``band_factor_batch_dev`` (the same B) on device
+        vectors of n + m values, ``stride_rhs`` doubles apart (0: one right-hand side for all) and ``stride_sol`` apart (None:
+        n + m).  Not waited for; an entry whose factorisation failed leaves its slice of ``d_sol`` untouched and does not stop
+        the others."""
+        stride_sol = self.plan.n + self.plan.m if stride_sol is None else stride_sol
+        self.ctx.check(self.ctx.lib.pk_band_solve_batch_dev(self.ctx.handle, int(B), d_rhs, int(stride_rhs), d_sol, int(stride_sol)))
+
+    def band_record_batch(self, B):
+        """The records of the last batch factorisation and solve, ``(B, 8)`` (row e: ``band_record``'s 8 doubles of entry e),
+        waited for, in one transfer."""
+        rec = np.empty((int(B), 8))
+        self.ctx.check(self.ctx.lib.pk_band_record_batch(self.ctx.handle, int(B), runtime.as_dp(rec)))
+        return rec
+
     # ------------------------------------------------------------------ the slacks of a resident iterate (csrc/pk_slack.cpp)
     def slack_reduce_dev(self, d_g, d_s, d_lam, d_sigma_s, d_rbar_s, d_s2, d_b2, d_out, stream=None):
         """Enqueue the elimination of the slacks on device pointers: ``s2`` and ``b2`` of the step's system
@@ -2068,6 +2093,38 @@ class Linearization:
         dp = runtime.as_dp
         ev.ctx.check(ev.ctx.lib.pk_solve_banded(ev.ctx.handle, dp(s1), dp(s2), dp(b), dp(x), dp(rec)))
         return x, BandInfo(rec, x, self.n)
+
+    def solve_banded_batch(self, b, s1=None, s2=None):
+        """``solve_banded`` for B systems (1 ... 16) that share this linearization's J and H and differ in ``s1``, ``s2`` and
+        ``b``, factored and solved in ONE launch sequence (the launches of one system, B times the workgroups each).  ``b``:
+        ``(B, n + m)``; ``s1``: None, a scalar, ``(n,)`` or ``(B, n)``; ``s2`` the same with m.  Returns ``(X, infos)``: ``X`` of
+        shape ``(B, n + m)`` and a list of B ``BandInfo``; row e has the bits ``solve_banded(b[e], s1[e], s2[e])`` returns, and is
+        all NaN unless ``infos[e].status == "solved"`` -- an entry that fails does not stop the others.  The ordering and its
+        ``ValueError``s are ``solve_banded``'s."""
+        from .band import BandOrdering
+
+        ev = self._check_live(True)
+        ev._kkt(True)
+        size = self.n + self.m
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.ndim != 2 or b.shape[1] != size or not 1 <= b.shape[0] <= 16:
+            raise ValueError(f"b must have shape (B, {size}) with B in 1 ... 16")
+        B = b.shape[0]
+
+        def rows(s, length, name):
+            s = np.zeros(length) if s is None else np.asarray(s, dtype=np.float64)
+            if s.ndim == 2 and s.shape != (B, length):
+                raise ValueError(f"{name} must be a scalar, ({length},) or ({B}, {length})")
+            return np.ascontiguousarray(np.broadcast_to(s, (B, length)))
+
+        s1, s2 = rows(s1, self.n, "s1"), rows(s2, self.m, "s2")
+        free = np.asarray(ev.plan.v_lb, dtype=np.float64) != np.asarray(ev.plan.v_ub, dtype=np.float64)
+        ordering = BandOrdering(ev.csr_map("jac"), ev.csr_map("hess"), free)
+        ev.band_plan(ordering)
+        X, rec = np.full((B, size), np.nan), np.empty((B, 8))
+        dp = runtime.as_dp
+        ev.ctx.check(ev.ctx.lib.pk_solve_banded_batch(ev.ctx.handle, B, dp(s1), dp(s2), dp(b), dp(X), dp(rec)))
+        return X, [BandInfo(rec[e], X[e], self.n) for e in range(B)]
 
     # ---- the dual side of optimality, and the first block of the KKT right-hand side (csrc/pk_ipm.cpp)
     def dual_residual(self, grad, lam, z=None, negate=False):

@@ -42,7 +42,16 @@ solves into the step, and the 64-byte record comes down.  A status other than 0 
 failed attempt, as ``splu``'s ``RuntimeError`` is on the direct path.  No CSR value, ``Sigma_x``, ``S2`` or right-hand side is
 downloaded.  LIMIT: pivoting is confined to the band part.  A model whose band part (K without the border's rows and
 columns) is singular while K is not gets failed attempts here and should use ``"direct"``; so should a model whose
-half-bandwidth exceeds 192 or whose border exceeds 8 unknowns (``BandOrdering`` raises ``ValueError``)."""
+half-bandwidth exceeds 192 or whose border exceeds 8 unknowns (``BandOrdering`` raises ``ValueError``).
+
+``band_attempts=k`` (1 ... 8, with ``"banded"`` only).  A factorisation is a long serial chain of small
+launches, and the schedule of ``delta_w`` is known in advance, so the next k candidates can be factored and solved together:
+``band_factor_batch_dev`` / ``band_solve_batch_dev`` take k matrices ``H + Sigma_x + delta_j`` over one J, H, ``S2`` and
+right-hand side in the launches of one, the k records come down in one transfer, and the candidates are then walked in the
+schedule's order with the same curvature test; the first that passes is the step.  Every entry of a batch has the bits of the
+single factorisation, so the iterates, the iteration count and ``regularisations`` do not depend on k.  What it costs: up to
+k - 1 factorisations and solves nobody needed (the candidates behind the accepted one), and k bands of device memory instead of
+one.  1, the default, is the path without a batch."""
 from __future__ import annotations
 
 import math
@@ -58,6 +67,7 @@ KAPPA_CURV = 1e-11           # the inertia-free curvature test
 KAPPA_SIGMA = 1e10           # the multiplier safeguard of slack_update_dev
 ARMIJO, MAX_TRIALS, TRIAL_BATCH = 1e-8, 25, 8
 MAX_REGULARISATIONS = 12
+MAX_BAND_ATTEMPTS = 8        # candidates of the schedule taken together with linear_solver="banded" (the unit's cap is 16)
 FIXED_S1 = 1e20              # the unit row of a fixed variable on the MINRES path
 STATUS = {0: "converged", -1: "maximum number of iterations", -2: "no acceptable step (restoration is not implemented)",
           -13: "a non-finite value"}
@@ -163,6 +173,25 @@ class Regularisation:
     def accept(self, delta):
         if delta > 0.0:
             self.last = delta
+
+    def schedule(self):
+        """The ``delta_w`` that ``attempts()`` would yield for one step, as a list, without counting any of them: the schedule
+        is a function of ``last`` alone."""
+        ahead = Regularisation()
+        ahead.last = self.last
+        return list(ahead.attempts())
+
+    def batches(self, k):
+        """The schedule of one step, k values at a time (the last batch is shorter where k does not divide), without counting.
+        Whoever takes candidates together walks each batch in order, calls ``tried(delta)`` for every candidate it looks at and
+        ``accept(delta)`` for the one that passed: ``last`` and ``count`` then end as ``attempts()`` leaves them."""
+        values = self.schedule()
+        for lo in range(0, len(values), int(k)):
+            yield values[lo: lo + int(k)]
+
+    def tried(self, delta):
+        if delta > 0.0:
+            self.count += 1
 
 
 def make_info(status, **fields):
@@ -329,7 +358,7 @@ def _errors(q, m):
     return e_0, e_mu, (bad > 0.0 or not finite)
 
 
-def solve(system, guess, optimizer_options=None, *, linear_solver="direct"):
+def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band_attempts=1):
     """Solve the NLP of ``system`` from ``guess`` (the shapes of ``ipopt.solve``); returns ``(solution, info)``.  ``info`` has
     cyipopt's keys ``x, g, obj_val, mult_g, mult_x_L, mult_x_U, status, status_msg`` and ``iterations``, ``mu``, ``error`` (the
     final E_0), ``linear_iterations`` (MINRES iterations in all; 0 on the direct and banded paths), ``regularisations``, and the slacks with
@@ -337,9 +366,15 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct"):
     -1 maximum iterations, -2 no acceptable step, -13 a non-finite value.  Options: ``tol`` (1e-8), ``max_iter`` (200),
     ``mu_init`` (0.1), ``print_level`` (0; 1 prints a line per iteration, 2 the step's figures as well, 3 every trial point).  ``linear_solver``: "direct", "minres" or
     "banded" (module docstring: where the latter two work); with "banded" a ``ValueError`` of the ordering (band too wide, border
-    too large) leaves the choice of "direct" to the caller."""
+    too large) leaves the choice of "direct" to the caller.  ``band_attempts`` (1 ... 8, "banded" only): how many ``delta_w`` of the
+    regularisation schedule are factored and solved together (module docstring); the iterates do not depend on it."""
     if linear_solver not in ("direct", "minres", "banded"):
         raise ValueError('linear_solver must be "direct", "minres" or "banded"')
+    if isinstance(band_attempts, bool) or not isinstance(band_attempts, (int, np.integer)) or not 1 <= band_attempts <= MAX_BAND_ATTEMPTS:
+        raise ValueError(f"band_attempts must be an integer in 1 ... {MAX_BAND_ATTEMPTS}")
+    if band_attempts != 1 and linear_solver != "banded":
+        raise ValueError('band_attempts other than 1 needs linear_solver="banded"')
+    band_attempts = int(band_attempts)
     opt = options(optimizer_options)
     x0, bare, _ = preprocess(system, guess, None)
     R = _Resident(system, x0)
@@ -358,6 +393,19 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct"):
     g0 = R.down(R.g, m)
     R.s = R.up(np.where(R.ineq, push_inside(g0, R.c_lb, R.c_ub), 0.0))
     reg = Regularisation()
+
+    def passes(delta):
+        """ds and the curvature test on the step in ``R.sol`` with ``R.s1 = Sigma_x + delta``: ``(curvature, delta)`` or None."""
+        ev.apply_operator_dev("H", at(R.ch), at(R.sol), at(R.w))
+        ev.slack_recover_dev(at(R.sol, n), at(R.lam), at(R.rbar_s), at(R.s2), at(R.sig_s), at(R.sol), at(R.w), at(R.s1), at(R.ds), at(R.rec, 44))
+        R.to_torch()
+        rc = R.down(R.rec)[44:49]
+        curvature, step_sq = rc[0] + rc[1], rc[2] + rc[3]
+        if rc[4] == 0.0 and np.all(np.isfinite(rc)) and curvature >= KAPPA_CURV * step_sq:
+            reg.accept(delta)
+            return curvature, delta
+        return None
+
     iterations = linear_iterations = 0
     status, e_0 = -1, math.inf
     while True:
@@ -385,7 +433,29 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct"):
             hvals, jvals, sig_x, s2, rhs = (R.down(t, c).copy() for t, c in ((R.ch, R.map_h.nnz), (R.cj, R.map_j.nnz), (R.sig_x, n), (R.s2, m),
                                                                               (R.rhs, n + m)))
         step = None
-        for delta in reg.attempts():
+        # ---- band_attempts > 1: the next candidates of the schedule factored and solved together, then walked in order
+        for deltas in (reg.batches(band_attempts) if band_attempts > 1 else ()):
+            k = len(deltas)
+            s1_rows = torch.stack([R.sig_x[:n] + delta for delta in deltas]) if n else torch.zeros((k, 1), dtype=torch.float64, device=R.dev)
+            sol_rows = torch.zeros((k, max(n + m, 1)), dtype=torch.float64, device=R.dev)
+            R.to_kernels()
+            ev.band_factor_batch_dev(k, at(R.ch), at(R.cj), at(s1_rows), at(R.s2), strides=(0, 0, n, 0))
+            ev.band_solve_batch_dev(k, at(R.rhs), at(sol_rows), stride_rhs=0, stride_sol=n + m)
+            records = ev.band_record_batch(k)
+            for j, delta in enumerate(deltas):
+                reg.tried(delta)
+                if records[j, 0] != 0.0 or not np.all(np.isfinite(records[j])):
+                    continue
+                R.s1, R.sol = s1_rows[j], sol_rows[j]
+                R.to_kernels()
+                step = passes(delta)
+                if step is not None:
+                    if opt["print_level"] > 1:
+                        print(f"      band batch of {k}: candidate {j} taken, delta_w {delta:.1e}")
+                    break
+            if step is not None:
+                break
+        for delta in (reg.attempts() if band_attempts == 1 else ()):
             R.s1 = R.sig_x + delta                        # (the curvature test's Sigma_x + delta_w)
             if direct is not None:
                 try:
@@ -432,14 +502,8 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct"):
                 R.to_torch()
                 R.sol[:n] *= R.free_mask[:n]
                 R.to_kernels()
-            ev.apply_operator_dev("H", at(R.ch), at(R.sol), at(R.w))
-            ev.slack_recover_dev(at(R.sol, n), at(R.lam), at(R.rbar_s), at(R.s2), at(R.sig_s), at(R.sol), at(R.w), at(R.s1), at(R.ds), at(R.rec, 44))
-            R.to_torch()
-            rc = R.down(R.rec)[44:49]
-            curvature, step_sq = rc[0] + rc[1], rc[2] + rc[3]
-            if rc[4] == 0.0 and np.all(np.isfinite(rc)) and curvature >= KAPPA_CURV * step_sq:
-                reg.accept(delta)
-                step = (curvature, delta)
+            step = passes(delta)
+            if step is not None:
                 break
         if step is None:
             status = -2

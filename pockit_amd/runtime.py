@@ -155,6 +155,10 @@ PROTOTYPES = {
     "pk_band_solve_dev": (C.c_int, [vp, vp, vp]),
     "pk_band_record": (C.c_int, [vp, dp]),
     "pk_solve_banded": (C.c_int, [vp, dp, dp, dp, dp, dp]),
+    "pk_band_factor_batch_dev": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64]),
+    "pk_band_solve_batch_dev": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64]),
+    "pk_band_record_batch": (C.c_int, [vp, C.c_int32, dp]),
+    "pk_solve_banded_batch": (C.c_int, [vp, C.c_int32, dp, dp, dp, dp, dp]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -226,6 +230,8 @@ PROTOTYPES = {
                                    C.c_double, vp, vp]),
     "pk_band_fill_dev": (C.c_int, [vp, vp, vp, vp, vp, vp]),
     "pk_band_raw_dev": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]),
+    "pk_band_raw_batch_dev": (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
+                                        vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64]),
 }
 EXPORTS = list(PROTOTYPES)
 

@@ -6,7 +6,8 @@ on downloaded vectors -- what a caller writes without the units.  Needs an MI355
 
 ``--banded`` runs the rows of DESIGN.md section 23 instead: ``linear_solver="banded"`` alternating with ``"direct"`` on both
 sizes, and the host-landed time of one factorisation and of one solve of the band LU with their launches (``--append`` adds the
-rows to ``--out`` instead of replacing it).
+rows to ``--out`` instead of replacing it).  ``--banded-batch`` runs the rows of section 24: the batch forms of the band LU at
+B = 1, 2, 4, 8 against B single factorisations and solves in a row, and whole solves with ``band_attempts`` = 1, 2, 4.
 """
 import argparse
 import importlib
@@ -148,8 +149,82 @@ def banded_rows(args, models, ipm):
     return lines
 
 
+def banded_batch_rows(args, models, ipm):
+    """one batched factorisation and one batched solve at B = 1, 2, 4, 8 against B single ones in a row on
+    the same values (enqueue and wait, host-landed, alternating), then whole solves with ``band_attempts`` = 1, 2, 4."""
+    from pockit_amd.band import BandOrdering
+
+    lines = [f"ip_solve_probe --banded-batch: the batch forms of the band LU against the single forms; median [min, max] of {args.runs} runs each, "
+             f"alternating, host-landed (perf_counter around enqueue + wait and around whole solves)"]
+    for name, scheme, mesh, num_point in MODELS:
+        ns = importlib.import_module(f"pockit_amd.{scheme}")
+        system, _, guess = getattr(models, name)(ns, mesh, num_point)
+        lines.append(f"{name}({scheme}, {mesh}, {num_point}): n {system.plan.n}, m {system.plan.m}")
+        R = ipm._Resident(system, ipm.preprocess(system, guess, None)[0])
+        R.evaluate()
+        R.to_torch()
+        o = BandOrdering(R.map_j, R.map_h, R.free)
+        R.ev.band_plan(o)
+        n, m, torch = R.n, R.m, R.torch
+        R.s2 = R.up(np.where(R.ineq, 1.0, 0.0))
+        R.rhs = R.up(np.random.default_rng(3).standard_normal(n + m))
+        at, ev = R.at, R.ev
+        for B in (1, 2, 4, 8):
+            s1 = torch.stack([torch.ones(n, dtype=torch.float64, device=R.dev) * (1.0 + 0.25 * e) for e in range(B)])
+            sol, one = torch.zeros((B, n + m), dtype=torch.float64, device=R.dev), torch.zeros(n + m, dtype=torch.float64, device=R.dev)
+            R.to_kernels()
+            t = {"factor batch": [], "solve batch": [], "factor singles": [], "solve singles": []}
+            for _ in range(args.runs + 1):
+                t0 = time.perf_counter()
+                ev.band_factor_batch_dev(B, at(R.ch), at(R.cj), at(s1), at(R.s2))
+                ev.sync()
+                t1 = time.perf_counter()
+                ev.band_solve_batch_dev(B, at(R.rhs), at(sol))
+                ev.sync()
+                t2 = time.perf_counter()
+                t["factor batch"].append(t1 - t0)
+                t["solve batch"].append(t2 - t1)
+                tf = ts = 0.0
+                for e in range(B):
+                    t0 = time.perf_counter()
+                    ev.band_factor_dev(at(R.ch), at(R.cj), at(s1[e]), at(R.s2))
+                    ev.sync()
+                    t1 = time.perf_counter()
+                    ev.band_solve_dev(at(R.rhs), at(one))
+                    ev.sync()
+                    tf, ts = tf + (t1 - t0), ts + (time.perf_counter() - t1)
+                t["factor singles"].append(tf)
+                t["solve singles"].append(ts)
+            records = ev.band_record_batch(B)
+            R.to_torch()
+            same = bool(torch.equal(sol[B - 1], one))
+            med = {k: statistics.median(v[1:]) for k, v in t.items()}
+            lines.append(f"    B {B}: factor batch {spread(t['factor batch'][1:], 1e3, '9.3f')} ms, {B} singles {spread(t['factor singles'][1:], 1e3, '9.3f')} ms, "
+                         f"ratio t_batch / (B t_single) {med['factor batch'] / med['factor singles']:.3f}; solve batch {spread(t['solve batch'][1:], 1e3, '9.3f')} ms, "
+                         f"{B} singles {spread(t['solve singles'][1:], 1e3, '9.3f')} ms, ratio {med['solve batch'] / med['solve singles']:.3f}; "
+                         f"statuses {[int(s) for s in records[:, 0]]}, last entry bit-equal to the single solve: {same}")
+        system.evaluator.close()
+        system, _, guess = getattr(models, name)(ns, mesh, num_point)
+        attempts = (1, 2, 4)
+        times, infos = {k: [] for k in attempts}, {}
+        ipm.solve(system, guess, linear_solver="banded")                    # warm-up
+        for _ in range(args.runs):
+            for k in attempts:
+                t0 = time.perf_counter()
+                _, infos[k] = ipm.solve(system, guess, linear_solver="banded", band_attempts=k)
+                times[k].append(time.perf_counter() - t0)
+        for k in attempts:
+            info = infos[k]
+            per = [x / max(1, info["iterations"]) for x in times[k]]
+            lines.append(f"    band_attempts {k}: {spread(times[k], 1e3)} ms per solve, {spread(per, 1e3, '9.2f')} ms per iteration; status {info['status']}, "
+                         f"{info['iterations']} Newton iterations, {info['regularisations']} regularised, f = {info['obj_val']:.10f}")
+        system.evaluator.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--banded-batch", action="store_true", help="the rows of the batched band LU instead (DESIGN.md section 24)")
     ap.add_argument("--banded", action="store_true", help="the rows of the banded step solver instead (DESIGN.md section 23)")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     ap.add_argument("--runs", type=int, default=5)
@@ -162,8 +237,8 @@ def main():
     from pockit_amd.optimizer import interior_point as ipm
     from pockit_amd.optimizer import scipy as scipy_solver
 
-    if args.banded:
-        text = "\n".join(banded_rows(args, models, ipm)) + "\n"
+    if args.banded or args.banded_batch:
+        text = "\n".join((banded_batch_rows if args.banded_batch else banded_rows)(args, models, ipm)) + "\n"
         print(text, end="")
         if args.out:
             with open(args.out, "a" if args.append else "w") as fh:
