@@ -6,7 +6,10 @@ factors the step's system on the device instead: no matri
 
 The problem is ``min f(x)  s.t.  g_i(x) = c_i`` on equality rows (``c_lb == c_ub``), ``g_i(x) - s_i = 0`` with
 ``c_lb_i <= s_i <= c_ub_i`` on inequality rows, ``v_lb <= x <= v_ub``; a variable with ``v_lb == v_ub`` is fixed and out of the
-system.  One iteration:
+system, and so is a slot of the NLP vector whose value the transcription dictates (``_common.dictated_slots``: a boundary value
+or time that is a number or a function of the static parameters).  Such a slot has no entry in J or H; left free it would be an
+empty row and column of the step's matrix.  For the length of a solve the evaluator's variable bounds hold ``lb == ub`` there
+(``set_bounds``), and the plan's bounds are put back when ``solve`` returns or raises.  One iteration:
 
 * ``cycle_dev`` / ``gather_csr_dev``: f, grad f, g and the CSR values of J and of the Lagrangian's Hessian;
 * ``ip_terms_dev`` on x and on s: ``Sigma``, ``rbar``, complementarity; ``dual_residual_dev``: ``r_d`` and ``b1``;
@@ -19,7 +22,8 @@ system.  One iteration:
   |ds|^2)``, on failure ``delta_w`` grows (``Regularisation``);
 * ``ip_step_dev`` on x and on s: the multiplier steps and the fraction-to-the-boundary lengths;
 * a backtracking line search on the l1 merit ``phi_mu + nu theta_1``: ``trial_points_dev``, the x-only batch
-  (``cycle_batch_dev``), ``slack_merit_dev``; ``4 B`` doubles and f come back;
+  (``cycle_batch_dev``), ``slack_merit_dev``; ``4 B`` doubles and f come back; a trial point with a non-finite f, g, grad f or
+  J is rejected like one outside the bounds;
 * ``slack_update_dev`` on x and on (s, lam) with the multiplier safeguard ``kappa = 1e10``.
 
 What is NOT here: a feasibility restoration phase, a filter, second-order corrections, Mehrotra steps, warm starts, sharded
@@ -58,7 +62,7 @@ import math
 
 import numpy as np
 
-from ._common import postprocess, preprocess
+from ._common import dictated_slots, postprocess, preprocess
 
 DEFAULTS = {"tol": 1e-8, "max_iter": 200, "mu_init": 0.1, "print_level": 0}
 KAPPA_PUSH = 1e-2            # kappa_1 = kappa_2 of the start's push inside the bounds
@@ -194,6 +198,14 @@ class Regularisation:
             self.count += 1
 
 
+def derivatives_finite(grad_batch, jac_batch, k, n, nnz_j):
+    """Are grad f and J finite at entry k of the line search's batch (torch tensors, dense ``[B][n]`` and ``[B][nnz_J]``)?  On
+    the edge of a model's domain f and g can be finite where a derivative is not (``sqrt`` at 0): such a trial point may pass
+    the Armijo test, and adopting it ends the solve with status -13 one iteration later.  It is rejected like a point outside."""
+    grad, jac = grad_batch[k * n: (k + 1) * n], jac_batch[k * nnz_j: (k + 1) * nnz_j]
+    return bool(grad.isfinite().all().item()) and bool(jac.isfinite().all().item())
+
+
 def make_info(status, **fields):
     info = dict(fields, status=int(status), status_msg=STATUS[int(status)])
     missing = [k for k in INFO_KEYS if k not in info]
@@ -263,12 +275,19 @@ class _Resident:
             raise NotImplementedError("the interior-point solver is not offered for a sharded evaluator")
         self.n, self.m = n, m = p.n, p.m
         self.dev = torch.device("cuda", int(getattr(ev, "device", 0)))
-        self.v_lb, self.v_ub, self.c_lb, self.c_ub = (np.asarray(a, dtype=np.float64) for a in (p.v_lb, p.v_ub, p.c_lb, p.c_ub))
+        self.v_lb, self.v_ub, self.c_lb, self.c_ub = (np.array(a, dtype=np.float64) for a in (p.v_lb, p.v_ub, p.c_lb, p.c_ub))
+        # a slot whose value the transcription dictates is a variable of the NLP vector that nothing reads: no entry in J or H,
+        # bounds (-inf, inf) or the state's.  Left free it is an empty row and column of K, so it is fixed
+        # here: at the dictated value (FIXED), at the start's value (FUNC: the kernels substitute the real one)
+        fixed_at, fixed_to, func = dictated_slots(system)
+        func_at = np.array([slot for slot, _, _ in func], dtype=np.int64)
+        x0 = np.array(x0, dtype=np.float64)
+        self.v_lb[fixed_at] = self.v_ub[fixed_at] = fixed_to
+        self.v_lb[func_at] = self.v_ub[func_at] = np.where(np.isfinite(x0[func_at]), x0[func_at], 0.0)
         self.free = self.v_lb != self.v_ub
         self.ineq = self.c_lb != self.c_ub
         if np.any(self.ineq & ~np.isfinite(self.c_lb) & ~np.isfinite(self.c_ub)):
             raise ValueError("a constraint row without a finite bound constrains nothing: drop it from the model")
-        ev.set_bounds()
         self.map_j, self.map_h = ev.csr_map("jac"), ev.csr_map("hess")
         for op in ("J", "JT", "H"):
             ev._operator(op)
@@ -291,6 +310,7 @@ class _Resident:
         self.minv = z(n + m)
         self.rec = z(64)
         self.batch = None
+        ev.set_bounds(v_lb=self.v_lb, v_ub=self.v_ub)       # (last: solve() puts the plan's back once this has been said)
 
     def zeros(self, count):
         return self.torch.zeros(max(int(count), 1), dtype=self.torch.float64, device=self.dev)
@@ -378,6 +398,14 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
     opt = options(optimizer_options)
     x0, bare, _ = preprocess(system, guess, None)
     R = _Resident(system, x0)
+    try:
+        return _iterate(system, R, opt, bare, linear_solver, band_attempts)
+    finally:
+        R.ev.set_bounds()            # the plan's bounds again: a later merit_scan measures against them, not against the fixed slots
+
+
+def _iterate(system, R, opt, bare, linear_solver, band_attempts):
+    """The loop of ``solve`` on the resident iterate ``R``."""
     ev, at, torch, n, m = R.ev, R.at, R.torch, R.n, R.m
     tol, mu = opt["tol"], opt["mu_init"]
     direct = DirectKkt(R.map_j, R.map_h, R.free) if linear_solver == "direct" else None
@@ -395,7 +423,8 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
     reg = Regularisation()
 
     def passes(delta):
-        """ds and the curvature test on the step in ``R.sol`` with ``R.s1 = Sigma_x + delta``: ``(curvature, delta)`` or None."""
+        """ds and the curvature test on the step in ``R.sol`` with ``R.s1 = Sigma_x + delta``: ``(curvature, delta, |step|^2)`` or
+        None."""
         ev.apply_operator_dev("H", at(R.ch), at(R.sol), at(R.w))
         ev.slack_recover_dev(at(R.sol, n), at(R.lam), at(R.rbar_s), at(R.s2), at(R.sig_s), at(R.sol), at(R.w), at(R.s1), at(R.ds), at(R.rec, 44))
         R.to_torch()
@@ -403,7 +432,7 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
         curvature, step_sq = rc[0] + rc[1], rc[2] + rc[3]
         if rc[4] == 0.0 and np.all(np.isfinite(rc)) and curvature >= KAPPA_CURV * step_sq:
             reg.accept(delta)
-            return curvature, delta
+            return curvature, delta, step_sq
         return None
 
     iterations = linear_iterations = 0
@@ -553,12 +582,13 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
                     print(f"        alpha {alpha:.3e}: f {f_trial[k]!r} log_sum {t[k, 2]!r} theta_1 {t[k, 0]!r} bad {t[k, 3]} merit - merit_0 "
                           f"{f_trial[k] - mu * t[k, 2] + nu * t[k, 0] - merit_0:.3e} predicted {alpha * slope_merit:.3e}")
             for k, alpha in enumerate(alphas[:tried]):
-                if t[k, 3] == 0.0 and armijo(f_trial[k] - mu * t[k, 2] + nu * t[k, 0], merit_0, alpha, slope_merit):
+                if (t[k, 3] == 0.0 and armijo(f_trial[k] - mu * t[k, 2] + nu * t[k, 0], merit_0, alpha, slope_merit)
+                        and derivatives_finite(gradB, jacB, k, n, system.plan.nnz_J)):
                     accepted = alpha
                     break
             done += tried
         if opt["print_level"] > 1:
-            print(f"      step: delta_w {step[1]:.1e} curvature {curvature:.3e} step_sq {step_sq:.3e} alpha_max {alpha_max:.3e} alpha_d {alpha_d:.3e} slope {slope:.3e} "
+            print(f"      step: delta_w {step[1]:.1e} curvature {curvature:.3e} step_sq {step[2]:.3e} alpha_max {alpha_max:.3e} alpha_d {alpha_d:.3e} slope {slope:.3e} "
                   f"nu {nu:.3e} theta_1 {theta_1:.3e} accepted {accepted} after {done} trial points")
         if accepted is None:
             status = -2

@@ -9,7 +9,8 @@
   bound leaves room for SLSQP's own accuracy and is four orders below the 6.5e-3 gap to the unconstrained optimum, so a solver
   that ignores the constraint fails --, an inequality row active, its multiplier non-zero.
 * every converged case: ``E_0 <= tol`` recomputed here with NumPy on the oracle's f, grad f, g and J from ``info`` alone, bound
-  multipliers >= 0, x inside its bounds.
+  multipliers >= 0, x inside its bounds; a slot whose value the transcription dictates is no variable of the problem: it holds
+  the dictated number and has no bound multiplier.
 * ``max_iter = 3`` on the brachistochrone: status -1, a finite x, no exception.
 
 The solves cap at ``max_iter = 200`` and assert no iteration count."""
@@ -39,8 +40,19 @@ def constrained_lqr(ns, mesh, num_point):
     return system, [phase], [ns.constant_guess(phase, 0.0), [0.0]]
 
 
-def error_from_info(ref, info):
-    """E_0 of the module's docstring from ``info`` alone, every function value from the oracle system ``ref``."""
+def dictated(system):
+    """``(fixed_at, fixed_to, func_at)`` of a ``pockit_amd`` system: the NLP slots whose value the transcription dictates (a
+    number; a function of the static parameters).  The solver fixes them; they are not variables of the problem."""
+    from pockit_amd.optimizer._common import dictated_slots
+
+    fixed_at, fixed_to, func = dictated_slots(system)
+    return fixed_at, fixed_to, np.array([slot for slot, _, _ in func], dtype=np.int64)
+
+
+def error_from_info(ref, info, dictated=None):
+    """E_0 of the module's docstring from ``info`` alone, every function value from the oracle system ``ref``.  ``dictated``
+    (what ``dictated(system)`` returns): those slots are not free, hold the dictated number where there is one, and have no bound
+    multiplier."""
     x, lam = info["x"], info["mult_g"]
     zl, zu, s, yl, yu = info["mult_x_L"], info["mult_x_U"], info["slack"], info["mult_s_L"], info["mult_s_U"]
     v_lb, v_ub, c_lb, c_ub = (np.asarray(a, dtype=np.float64) for a in (ref.v_lb, ref.v_ub, ref.c_lb, ref.c_ub))
@@ -48,6 +60,12 @@ def error_from_info(ref, info):
     g, grad = ref.constraints(x), ref.gradient(x)
     J = scipy.sparse.coo_array((ref.jacobian(x), ref.jacobianstructure()), shape=(m, n)).tocsr()
     free, ineq = v_lb != v_ub, c_lb != c_ub
+    if dictated is not None:
+        fixed_at, fixed_to, func_at = dictated
+        dead = np.concatenate((fixed_at, func_at))
+        free[dead] = False
+        assert np.array_equal(x[fixed_at], fixed_to), (x[fixed_at], fixed_to)
+        assert not zl[dead].any() and not zu[dead].any(), (zl[dead], zu[dead])
     r_d = np.where(free, grad + J.T @ lam - zl + zu, 0.0)
     r_s = np.where(ineq, -lam - yl + yu, 0.0)
     theta = np.where(ineq, g - s, g - c_lb)
@@ -66,9 +84,9 @@ def error_from_info(ref, info):
     return e_0
 
 
-def _converged(ref, info):
+def _converged(ref, info, dictated=None):
     assert info["status"] == 0, (info["status"], info["status_msg"], info["iterations"], info["error"])
-    assert info["error"] <= TOL and error_from_info(ref, info) <= TOL
+    assert info["error"] <= TOL and error_from_info(ref, info, dictated=dictated) <= TOL
     x = info["x"]
     assert np.all(x >= np.asarray(ref.v_lb)) and np.all(x <= np.asarray(ref.v_ub))
     assert np.all(info["mult_x_L"] >= 0.0) and np.all(info["mult_x_U"] >= 0.0) and np.all(info["mult_s_L"] >= 0.0) and np.all(info["mult_s_U"] >= 0.0)
@@ -98,7 +116,7 @@ def test_lqr_reaches_the_riccati_value(riccati, linear_solver):
     ns = _ns("lobatto", "pockit_amd")
     system, (phase,), _ = models.lqr(ns, 6, 6)
     (var, s), info = _solve(system, [ns.constant_guess(phase, 0.0), [0.0]], linear_solver=linear_solver)
-    _converged(models.lqr(_ns("lobatto", "oracle"), 6, 6)[0], info)
+    _converged(models.lqr(_ns("lobatto", "oracle"), 6, 6)[0], info, dictated=dictated(system))
     assert abs(info["obj_val"] - riccati) <= 2e-6 * max(1.0, abs(riccati)), (info["obj_val"], riccati)
     assert abs(var.x[0][-1] - s[0]) < 1e-9 and abs(var.x[0][0] - 1.0) < 1e-12
     assert (info["linear_iterations"] > 0) == (linear_solver == "minres")
@@ -112,7 +130,7 @@ def test_the_brachistochrone_reaches_the_cycloid_time(scheme, mesh, num_point):
     (var,), info = _solve(system, guess)
     theta = brentq(lambda t: (t - np.sin(t)) / (1 - np.cos(t)) - 1.0, 0.1, 2 * np.pi - 0.1)      # x_f / y_f = 1
     optimum = theta * np.sqrt(2.0 / (1 - np.cos(theta)) / 9.81)
-    _converged(models.brachistochrone(_ns(scheme, "oracle"), mesh, num_point)[0], info)
+    _converged(models.brachistochrone(_ns(scheme, "oracle"), mesh, num_point)[0], info, dictated=dictated(system))
     assert abs(info["obj_val"] - optimum) <= 1e-7, (info["obj_val"], optimum)
     assert abs(var.t_f - optimum) <= 1e-7
     assert abs(var.x[0][-1] - 2.0) < 1e-12 and abs(var.x[1][-1] - 2.0) < 1e-12
@@ -142,7 +160,7 @@ def test_lqr_with_an_active_path_inequality_matches_slsqp_on_the_oracle(scheme, 
     c_lb, c_ub = np.asarray(ref.c_lb), np.asarray(ref.c_ub)
     assert int(np.sum(c_lb != c_ub)) == rows
     _, info = _solve(system, guess)
-    _converged(ref, info)
+    _converged(ref, info, dictated=dictated(system))
     res = _slsqp(ref, models.pack_guess(ref, ref_guess))
     print(f"interior point {info['obj_val']!r}, SLSQP {res.fun!r}, difference {abs(info['obj_val'] - res.fun):.2e}")
     assert abs(info["obj_val"] - res.fun) <= 1e-6

@@ -10,7 +10,7 @@ import pytest
 
 import models
 import sparse_cases as sc
-from test_gpu_interior_point import TOL, _converged, _ns, constrained_lqr
+from test_gpu_interior_point import TOL, _converged, _ns, constrained_lqr, dictated
 from test_gpu_interior_point_banded import _no_matrix_came_down, downloads  # noqa: F401  (downloads: a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -46,7 +46,7 @@ def test_the_solve_does_not_depend_on_band_attempts(build, downloads):
         finally:
             system.evaluator.close()
         assert info["status"] == 0, (k, info["status_msg"])
-        _converged(build("oracle")[0], info)
+        _converged(build("oracle")[0], info, dictated=dictated(system))
         _no_matrix_came_down(system, downloads, info["iterations"])
         runs.append(info)
     first = runs[0]

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import models
-from test_gpu_interior_point import TOL, _converged, _ns, _slsqp, constrained_lqr, riccati  # noqa: F401  (riccati: a fixture)
+from test_gpu_interior_point import TOL, _converged, _ns, _slsqp, constrained_lqr, dictated, riccati  # noqa: F401  (riccati: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -68,7 +68,7 @@ def test_lqr_reaches_the_riccati_value(riccati, downloads):
     ns = _ns("lobatto", "pockit_amd")
     system, (phase,), _ = models.lqr(ns, 6, 6)
     (var, s), info = _solve(system, [ns.constant_guess(phase, 0.0), [0.0]])
-    _converged(models.lqr(_ns("lobatto", "oracle"), 6, 6)[0], info)
+    _converged(models.lqr(_ns("lobatto", "oracle"), 6, 6)[0], info, dictated=dictated(system))
     assert abs(info["obj_val"] - riccati) <= 2e-6 * max(1.0, abs(riccati)), (info["obj_val"], riccati)
     assert abs(var.x[0][-1] - s[0]) < 1e-9 and abs(var.x[0][0] - 1.0) < 1e-12
     assert info["linear_iterations"] == 0
@@ -83,7 +83,7 @@ def test_the_brachistochrone_reaches_the_cycloid_time(scheme, mesh, num_point, d
     (var,), info = _solve(system, guess)
     theta = brentq(lambda t: (t - np.sin(t)) / (1 - np.cos(t)) - 1.0, 0.1, 2 * np.pi - 0.1)      # x_f / y_f = 1
     optimum = theta * np.sqrt(2.0 / (1 - np.cos(theta)) / 9.81)
-    _converged(models.brachistochrone(_ns(scheme, "oracle"), mesh, num_point)[0], info)
+    _converged(models.brachistochrone(_ns(scheme, "oracle"), mesh, num_point)[0], info, dictated=dictated(system))
     assert abs(info["obj_val"] - optimum) <= 1e-7, (info["obj_val"], optimum)
     assert abs(var.t_f - optimum) <= 1e-7
     assert abs(var.x[0][-1] - 2.0) < 1e-12 and abs(var.x[1][-1] - 2.0) < 1e-12
@@ -97,7 +97,7 @@ def test_lqr_with_an_active_path_inequality_matches_slsqp_on_the_oracle(scheme, 
     c_lb, c_ub = np.asarray(ref.c_lb), np.asarray(ref.c_ub)
     assert int(np.sum(c_lb != c_ub)) == rows
     _, info = _solve(system, guess)
-    _converged(ref, info)
+    _converged(ref, info, dictated=dictated(system))
     res = _slsqp(ref, models.pack_guess(ref, ref_guess))
     print(f"interior point {info['obj_val']!r}, SLSQP {res.fun!r}, difference {abs(info['obj_val'] - res.fun):.2e}")
     assert abs(info["obj_val"] - res.fun) <= 1e-6

@@ -157,3 +157,23 @@ def test_without_a_gpu_solve_fails_loudly():
     system, (phase,), _ = models.lqr(lobatto, 2, 3)
     with pytest.raises(RuntimeError):
         ipm.solve(system, [lobatto.constant_guess(phase, 0.0), [0.0]])
+
+
+def test_a_trial_point_with_a_non_finite_derivative_is_told_apart():
+    """``derivatives_finite`` looks at entry k of the line search's dense batches and at nothing else."""
+    import torch
+
+    n, nnz = 5, 7
+    grad = torch.arange(3 * n, dtype=torch.float64)
+    jac = torch.arange(3 * nnz, dtype=torch.float64)
+    assert all(ipm.derivatives_finite(grad, jac, k, n, nnz) for k in range(3))
+    for bad in (float("inf"), float("-inf"), float("nan")):
+        for at in (n, 2 * n - 1):
+            g = grad.clone()
+            g[at] = bad
+            assert [ipm.derivatives_finite(g, jac, k, n, nnz) for k in range(3)] == [True, False, True]
+        for at in (nnz, 2 * nnz - 1):
+            j = jac.clone()
+            j[at] = bad
+            assert [ipm.derivatives_finite(grad, j, k, n, nnz) for k in range(3)] == [True, False, True]
+    assert ipm.derivatives_finite(grad, jac[:0], 0, n, 0)
