@@ -5,6 +5,8 @@ expressions, kind tables scaled by d_j/2, scalar items, lambda gathers -- but wi
 host.  It lets the CPU test-suite validate the transcription compiler (layout *and* value
 expressions) against the oracle / golden vectors without a GPU.  Never used by the product.
 """
+import weakref
+
 import numpy as np
 import sympy as sp
 
@@ -12,12 +14,45 @@ from pockit_amd.model import FIXED, FREE
 from pockit_amd.transcription import DT, SIG, TAU, WQ, lam_path, lam_sys, ltb_sym, ltf_sym, mu_sym
 
 
-def _bc_value(info, cur, sdict):
+_FNS = weakref.WeakKeyDictionary()      # plan -> {key: lambdified function}: evaluating one plan at many points (a NaN sweep)
+                                        # would otherwise spend its time in lambdify
+
+
+def _fn(plan, key, syms, make):
+    fns = _FNS.setdefault(plan, {})
+    key = (key, tuple(syms))
+    if key not in fns:
+        # (joint CSE with SymPy's "basic" optimizations, as the code generator and the oracle print their bodies: its
+        #  preprocessing cancels a derivative that is identically zero term by term, so such an entry stays finite at a
+        #  non-finite point in all three)
+        fns[key] = sp.lambdify(syms, make(), modules="numpy", cse=lambda exprs: sp.cse(exprs, optimizations="basic"))
+    return fns[key]
+
+
+def _bc_value(info, cur, sdict, plan):
     if info.t == FREE:
         return cur
     if info.t == FIXED:
         return info.v
-    return float(info.v.expr.subs(sdict))
+    syms = list(sdict)                  # (lambdify: IEEE values at an infinite or NaN static parameter, as in _eval_sys)
+    with np.errstate(all="ignore"):
+        return float(_fn(plan, ("bc", info.v.expr), syms, lambda: [info.v.expr])(*[np.float64(sdict[s_]) for s_ in syms])[0])
+
+
+class _Tracked:
+    """An output array of ``Interp._run`` with a mask of the slots that were written (a NaN sentinel would take a NaN of
+    the model's own for a hole).  Supports what ``_run`` does: slice / index assignment and ``+=`` on one slot."""
+
+    def __init__(self, n):
+        self.values, self.written = np.zeros(n), np.zeros(n, dtype=bool)
+
+    def __setitem__(self, key, val):
+        self.values[key] = val
+        self.written[key] = True
+
+    def __getitem__(self, key):
+        assert np.all(self.written[key]), "a slot is read before it is written"
+        return self.values[key]
 
 
 class Interp:
@@ -43,13 +78,14 @@ class Interp:
         p, lay = pp.phase, pp.layout
         xp = self.x[plan.l_p[k]: plan.r_p[k]].copy()
         for i in range(p.n_x):
-            xp[lay.l_v[i]] = _bc_value(p.info_bc_0[i], xp[lay.l_v[i]], self.sdict)
-            xp[lay.r_v[i] - 1] = _bc_value(p.info_bc_f[i], xp[lay.r_v[i] - 1], self.sdict)
-        xp[-2] = _bc_value(p.info_t_0, xp[-2], self.sdict)
-        xp[-1] = _bc_value(p.info_t_f, xp[-1], self.sdict)
-        dt = xp[-1] - xp[-2]
-        tm = (xp[-1] + xp[-2]) / 2
-        return dict(xp=xp, dt=dt, t=(lay.tau - 0.5) * dt + tm, L_m=lay.L_m, base=pp.base())
+            xp[lay.l_v[i]] = _bc_value(p.info_bc_0[i], xp[lay.l_v[i]], self.sdict, plan)
+            xp[lay.r_v[i] - 1] = _bc_value(p.info_bc_f[i], xp[lay.r_v[i] - 1], self.sdict, plan)
+        xp[-2] = _bc_value(p.info_t_0, xp[-2], self.sdict, plan)
+        xp[-1] = _bc_value(p.info_t_f, xp[-1], self.sdict, plan)
+        with np.errstate(all="ignore"):      # (a non-finite t_0 or t_f)
+            dt = xp[-1] - xp[-2]
+            tm = (xp[-1] + xp[-2]) / 2
+            return dict(xp=xp, dt=dt, t=(lay.tau - 0.5) * dt + tm, L_m=lay.L_m, base=pp.base())
 
     def _eval_nodes(self, k, exprs, q):
         """Evaluate expressions (with placeholders) on nodes q of phase k."""
@@ -84,9 +120,9 @@ class Interp:
             vals[ltf_sym(i)] = np.full(len(q), float(np.dot(lay.Tf_val, self.lam[r0 + lay.Tf_row])))
             vals[ltb_sym(i)] = np.full(len(q), float(np.dot(lay.Tb_val, self.lam[r0 + lay.Tb_row])))
         syms = list(vals)
-        full = [sp.sympify(e).subs(env["base"]) for e in exprs]
-        fn = sp.lambdify(syms, full, modules="numpy")
-        out = fn(*[vals[s_] for s_ in syms])
+        fn = _fn(plan, (k, tuple(exprs)), syms, lambda: [sp.sympify(e).subs(env["base"]) for e in exprs])
+        with np.errstate(all="ignore"):
+            out = fn(*[vals[s_] for s_ in syms])
         return [np.broadcast_to(np.asarray(o, dtype=np.float64), q.shape) for o in out]
 
     def _mu(self, k):
@@ -111,12 +147,18 @@ class Interp:
         vals[SIG] = self.sigma
         for c in range(self.plan.n_sys):
             vals[lam_sys(c)] = self.lam[c]
-        return [float(sp.sympify(e).subs(vals)) for e in exprs]
+        if not exprs:
+            return []
+        # (lambdify, not float(expr.subs(...)): an infinite or NaN value gives IEEE results instead of a SymPy infinity)
+        syms = list(vals)
+        fn = _fn(self.plan, ("sys", tuple(exprs)), syms, lambda: [sp.sympify(e) for e in exprs])
+        with np.errstate(all="ignore"):
+            return [float(v) for v in fn(*[np.float64(vals[s_]) for s_ in syms])]
 
     def _run(self, cb, nnz, with_lambda, complete=True):
         plan = self.plan
-        out = np.full(nnz, np.nan)
-        for k, pp in enumerate(plan.phase_plans):
+        out = _Tracked(nnz)                                 # (which slots were written is kept beside the values: a
+        for k, pp in enumerate(plan.phase_plans):           #  written NaN is a value, an unwritten slot is a hole)
             lay = pp.layout
             if cb is plan.jac or cb is getattr(plan, "_jacc", None):
                 _, _, tv = lay.T_mid_structure()
@@ -160,7 +202,8 @@ class Interp:
                 v *= self.lam[it.lam]
             out[it.pos] = v
         if complete:
-            assert not np.isnan(out).any(), "plan does not cover every output slot"
+            assert out.written.all(), "plan does not cover every output slot"
+            return out.values
         return out
 
     def jacobian(self):
@@ -184,7 +227,8 @@ class Interp:
                         vals = np.concatenate([vals, B2[tr] * A2[tc] * m])
                 assert len(vals) == b.count
                 out[b.pos: b.pos + b.count] = vals
-            assert not np.isnan(out).any(), "plan does not cover every output slot"
+            assert out.written.all(), "plan does not cover every output slot"
+            out = out.values
         return out
 
     def jacobian_compact(self):

@@ -30,6 +30,7 @@ import numpy as np
 U = 2.0 ** -53
 BLOCK = 256                 # PK_BLOCK
 OP_GRID_CAP = 2048          # PK_LIB_GRID_CAP of csrc/pk_libkernel.h
+CSR_GRID_CAP = 4096         # the workgroups pk_csr is launched with at most (K_CSR in csrc/pk_launch.h)
 BUCKETS = (-40, -20, 0, 20, 40)
 
 # context -> model and the sizes the cases are built for (both test files assert them against the plan)
@@ -38,6 +39,11 @@ CONTEXTS = {
     "B": dict(model=("brachistochrone", "radau", 60, 5), n=1205, m=900, nnz_j=10177, nnz_h=1198, trip_j=13777),
     "C": dict(model=("brachistochrone", "radau", 200, 8), n=6405, m=4800, nnz_j=78365, nnz_h=6398, trip_j=111965),
 }
+# The context of the gather cases past pk_csr's grid cap: the smallest uniform mesh of the full-size CSR test's model whose
+# Jacobian has more than CSR_GRID_CAP * BLOCK + 512 triplets (2 775 intervals give 1 048 875).  Kept out of CONTEXTS: it has
+# no operator cases.
+CAP_CONTEXT = dict(model=("planar_quadrotor", "radau", 2776, 6), n=133256, m=133248, nnz_j=1049253, trip_j=1049253)
+GATHER_CAP_MUTANT = "second_trip_dropped"      # the stride loops of pk_csr left after their first trip
 OPERATOR_MUTANTS = ("slot", "row_boundary", "tree_stops_at_2", "strided_first_trip", "long_first_2048")
 GATHER_MUTANTS = ("remainder",)
 MUTANTS = OPERATOR_MUTANTS + GATHER_MUTANTS
@@ -286,12 +292,13 @@ class GatherCase:
     The value of each triplet is assigned after ``perm`` is drawn, from the bucket of the CSR entry whose run it falls in
     (entry p: bucket p mod 5)."""
 
-    def __init__(self, ctx, name, runs, seed, with_seg=True):
+    def __init__(self, ctx, name, runs, seed, with_seg=True, context=None):
         self.ctx, self.name, self.id = ctx, name, f"{ctx}-{name}"
+        self.context = CONTEXTS[ctx] if context is None else context
         rng = np.random.default_rng(seed)
         self.runs = np.asarray(runs, dtype=np.int64)
         self.n_unique, self.n_triplets = len(self.runs), int(self.runs.sum())
-        assert self.n_triplets == CONTEXTS[ctx]["trip_j"] and self.runs.min() >= 1, self.id
+        assert self.n_triplets == self.context["trip_j"] and self.runs.min() >= 1, self.id
         self.start = np.concatenate(([0], np.cumsum(self.runs)))
         self.perm = rng.permutation(self.n_triplets).astype(np.int32)
         if with_seg:
@@ -308,9 +315,10 @@ class GatherCase:
     @functools.cached_property
     def reference(self):
         """(ref, bound, scale) per CSR entry."""
-        t = self.triplets[self.perm].tolist()
-        ref, sabs = np.zeros(self.n_unique), np.zeros(self.n_unique)
-        for p in range(self.n_unique):
+        t = self.triplets[self.perm]
+        ref, sabs = t[self.start[:-1]].copy(), np.abs(t[self.start[:-1]])      # a run of one: the triplet itself, exactly
+        t = t.tolist()
+        for p in np.flatnonzero(self.runs > 1).tolist():
             run = t[self.start[p]: self.start[p + 1]]
             ref[p] = math.fsum(run)
             sabs[p] = math.fsum(abs(x) for x in run)
@@ -322,16 +330,21 @@ class GatherCase:
 
 def emulate_gather(case, mutant=None):
     """The CSR values as pk_csr computes them: the triplets of a run added sequentially in run order."""
-    assert mutant is None or mutant in GATHER_MUTANTS
+    assert mutant is None or mutant in GATHER_MUTANTS + (GATHER_CAP_MUTANT,)
     t = case.triplets[case.perm]
     if case.seg is None:
-        return t.copy()
-    width = np.repeat(case.slice_width, BLOCK)[: case.n_unique]        # the padded width of the entry's slice
-    trips = width - width % 4 if mutant == "remainder" else width      # (the unrolled loop without its remainder loop)
-    out = np.zeros(case.n_unique)
-    for k in range(int(case.runs.max())):
-        m = (case.runs > k) & (k < trips)
-        out[m] = out[m] + t[case.start[:-1][m] + k]
+        out = t.copy()
+    else:
+        width = np.repeat(case.slice_width, BLOCK)[: case.n_unique]        # the padded width of the entry's slice
+        trips = width - width % 4 if mutant == "remainder" else width      # (the unrolled loop without its remainder loop)
+        out = np.zeros(case.n_unique)
+        live = np.arange(case.n_unique)
+        for k in range(int(case.runs.max())):
+            live = live[case.runs[live] > k]                               # (the entries whose run has a k-th triplet)
+            m = live[k < trips[live]]
+            out[m] = out[m] + t[case.start[:-1][m] + k]
+    if mutant == GATHER_CAP_MUTANT:      # a workgroup serves slice b only, not b + 4096 ...: what it skips is never written
+        out[CSR_GRID_CAP * BLOCK:] = np.nan
     return out
 
 
@@ -375,3 +388,21 @@ def gather_cases():
     cases.append(GatherCase("B", "a-run-of-3000", runs, 8))
     cases.append(GatherCase("B", "no-seg", np.ones(tb, dtype=np.int64), 9, with_seg=False))
     return tuple(cases)
+
+
+@functools.lru_cache(maxsize=None)
+def gather_cap_cases():
+    """pk_csr past its grid cap of 4 096 workgroups, on CAP_CONTEXT: the second trip of the slice loop (a map with ``seg``)
+    and of the elementwise loop (``seg`` = NULL).  With ``seg``: n_unique = 1 048 577 + 255 = 4 097 whole slices, so slice
+    4 096 -- the one a workgroup reaches only on its second trip -- is also the last one; it holds a run of 2 and, in its last
+    entry, a run of 5 (the unrolled loop and its remainder on that trip).  Every other run is 1, except the one in slice 0
+    that takes up the triplets of the context the map must account for beyond that (pk_set_csr_map requires n_triplets =
+    nnz_J): workgroup 0 walks a wide slice and then takes its second trip."""
+    trip = CAP_CONTEXT["trip_j"]
+    n_unique = 1048577 + 255
+    runs = np.ones(n_unique, dtype=np.int64)
+    runs[CSR_GRID_CAP * BLOCK + 3], runs[n_unique - 1] = 2, 5
+    runs[7] += trip - int(runs.sum())
+    assert runs[7] > 1
+    return (GatherCase("D", "slices-past-the-cap", runs, 10, context=CAP_CONTEXT),
+            GatherCase("D", "no-seg-past-the-cap", np.ones(trip, dtype=np.int64), 11, with_seg=False, context=CAP_CONTEXT))

@@ -1064,6 +1064,38 @@ def test_device_csr_full_size_matches_host_gather():
     close(out.cpu().numpy(), mh.gather(H), 1e-14, what="H csr (gathered triplets)")
 
 
+def test_device_csr_gathers_past_the_grid_cap():
+    """pk_csr is launched with at most 4 096 workgroups of 256 threads: beyond 1 048 576 CSR entries a thread takes a second
+    trip of the stride loop.  Quadrotor 2776 x 6 -- the smallest uniform mesh of the full-size test's model with more than
+    1 048 576 + 512 Jacobian entries (found from the plan; 2775 intervals give 1 048 875) -- has no (row, col) repeats in J, so
+    its gather is the elementwise loop (csr_seg == NULL): bit for bit the host gather of the same triplets, entries past the cap
+    included, from device-resident triplets and through ``jacobian_csr``."""
+    import torch
+
+    cap = 4096 * 256
+    system, _, guess = models.planar_quadrotor(_ns("radau", "pockit_amd"), mesh=2776, num_point=6)
+    assert cap + 512 < system.plan.nnz_J == 1049253
+    x, _, _ = models.bench_inputs(system, guess)
+    ev = system.evaluator
+    J = np.array(ev.jacobian_direct(x))
+    mj = ev.csr_map("jac")
+    assert mj.seg is None and mj.nnz == system.plan.nnz_J
+    want = mj.gather(J)
+    assert np.count_nonzero(want[cap:]) > 256, "the entries past the cap must carry values"
+    dev = torch.device("cuda", 0)
+    dJ = torch.from_numpy(J).to(dev)
+    out = torch.full((mj.nnz + 16,), float("nan"), dtype=torch.float64, device=dev)      # NaN: an entry the loop skipped shows
+    out[:8] = out[-8:] = -7.25e77
+    torch.cuda.synchronize()
+    ev.gather_csr_dev("jac", dJ.data_ptr(), out.data_ptr() + 8 * 8)
+    ev.sync()
+    got = out.cpu().numpy()
+    assert np.all(got[:8] == -7.25e77) and np.all(got[-8:] == -7.25e77), "the gather wrote outside its output"
+    assert np.array_equal(got[8:-8], want), "device gather of the triplets"
+    assert np.array_equal(ev.jacobian_csr(x), want), "jacobian_csr"
+    system._invalidate()
+
+
 # ---------------------------------------------------------------------------------------------------------
 # the reference's own check tests (tests/test_radau/test_check_radau.py, tests/test_labatto/test_check_lobatto.py)
 # restated against the GPU-backed API

@@ -23,9 +23,11 @@ Gather cases (contexts A and B, which = 0): n_unique mod 256 in {0, 1, 255}; rag
 in {1, 2, 3, 4, 5, 7, 8, 9} (the four-way unrolled loop and its remainder at every width); one run of 3 000 among runs of 1; a
 slice of runs of 1 inside a map that has ``seg``; ``seg`` = NULL.  The same checks.
 
-What pk_csr leaves out here: its grid caps at 4 096 workgroups, so its stride loop needs more than 1 048 576 CSR entries.
-tests/test_gpu_parity.py::test_device_csr_full_size_matches_host_gather gathers n_unique = 755 925 (J, no repeats) and 83 995
-(H) at planar_quadrotor(radau, 2000, 6): neither exceeds the cap, so that loop's second trip is reached by no test.
+pk_csr past its grid cap (4 096 workgroups: a stride loop's second trip needs more than 1 048 576 CSR entries), in the context
+of planar_quadrotor(radau, 2776, 6) -- the smallest uniform mesh of that model with more than 1 048 576 + 512 Jacobian triplets:
+a map with ``seg`` of 1 048 577 + 255 entries (4 097 slices; slice 4 096 holds a run of 2 and, in its last entry, a run of 5;
+slice 0 a wide run: workgroup 0 takes both), and ``seg`` = NULL with 1 049 253 entries (the elementwise loop).  The same checks.
+tests/test_gpu_parity.py::test_device_csr_gathers_past_the_grid_cap gathers the model's real Jacobian at that size.
 
 The operator group and the gather group have an evaluator each per context: a synthetic pk_set_csr_map drops the operators, and
 after it the evaluator's cached CSR methods would describe a map the context no longer has -- they are not called here.
@@ -45,9 +47,10 @@ SENTINEL = -7.25e77
 
 
 def _evaluator(ctx):
-    name, scheme, mesh, num_point = sc.CONTEXTS[ctx]["model"]
+    c = sc.CAP_CONTEXT if ctx == "D" else sc.CONTEXTS[ctx]
+    name, scheme, mesh, num_point = c["model"]
     system = getattr(models, name)(importlib.import_module(f"pockit_amd.{scheme}"), mesh, num_point)[0]
-    c, plan = sc.CONTEXTS[ctx], system.plan
+    plan = system.plan
     assert (plan.n, plan.m, plan.nnz_J) == (c["n"], c["m"], c["trip_j"])
     return system.evaluator
 
@@ -146,7 +149,7 @@ def test_operator_kernels_match_the_exact_row_sums(case, operator_context):
     assert sc.same_bits(plain[empty], np.zeros(int(empty.sum()))) and sc.same_bits(added[empty], case.add[empty])
 
 
-@pytest.mark.parametrize("case", sc.gather_cases(), ids=lambda c: c.id)
+@pytest.mark.parametrize("case", sc.gather_cases() + sc.gather_cap_cases(), ids=lambda c: c.id)
 def test_gather_kernel_matches_the_exact_run_sums(case, gather_context):
     import torch
 

@@ -8,7 +8,9 @@ tests/test_gpu_sparse_kernels.py holds pk_op_rows, pk_op_long and pk_csr to.  CP
   1 / (4 (L + 1)**2 u), 1.3e5 at the longest row used) -- asserted, not assumed;
 * six deliberate mistakes in the emulator are each caught by the checker on at least one case;
 * the structures are what the block cutter sees: stream and piece counts and the number of long rows match a Python
-  transcription of pk_op_row_blocks.
+  transcription of pk_op_row_blocks;
+* the gather cases past pk_csr's grid cap really exceed it (more slices, and more entries, than 4 096 workgroups take in one
+  trip), and a stride loop left after its first trip is caught.
 """
 import math
 
@@ -203,3 +205,46 @@ def test_the_cases_reach_the_paths_they_are_named_for():
     for ctx in "AB":
         assert {c.op for c in OPERATOR_CASES if c.ctx == ctx and c.name != "no-src"} == {0, 1, 2}
     assert max(int(c.nnz) for c in OPERATOR_CASES) == 2100 * 257
+
+
+# ---------------------------------------------------------------- pk_csr past its grid cap
+def test_the_cap_context_matches_its_plan_and_is_the_smallest_mesh_past_the_cap():
+    import importlib
+
+    import models
+
+    c = sc.CAP_CONTEXT
+    name, scheme, mesh, num_point = c["model"]
+    ns = importlib.import_module(f"pockit_amd.{scheme}")
+    plan = getattr(models, name)(ns, mesh, num_point)[0].plan
+    assert (plan.n, plan.m, plan.nnz_J) == (c["n"], c["m"], c["trip_j"])
+    assert len(set(zip(plan.jac_row.tolist(), plan.jac_col.tolist()))) == c["nnz_j"] == c["trip_j"]      # J has no repeats: seg = NULL
+    assert plan.nnz_J > sc.CSR_GRID_CAP * sc.BLOCK + 512
+    assert getattr(models, name)(ns, mesh - 1, num_point)[0].plan.nnz_J <= sc.CSR_GRID_CAP * sc.BLOCK + 512
+
+
+@pytest.mark.parametrize("case", sc.gather_cap_cases(), ids=ids)
+def test_the_gather_cases_past_the_cap_take_a_second_trip(case):
+    nblk = -(-case.n_unique // sc.BLOCK)
+    assert sorted(case.perm.tolist()) == list(range(case.n_triplets))
+    ref, bound, scale = case.reference
+    got = case.emulated()
+    assert len(sc.failures(got, ref, bound)) == 0 and sc.same_bits(got[case.runs == 1], ref[case.runs == 1])
+    if case.seg is None:      # the elementwise loop: thread p, then p + 4 096 * 256
+        assert case.n_unique > sc.CSR_GRID_CAP * sc.BLOCK + 512
+    else:                     # the slice loop: workgroup b, then b + 4 096
+        assert nblk > sc.CSR_GRID_CAP, "the shape must exceed the cap"
+        assert case.n_unique == 1048577 + 255
+        late = np.flatnonzero(case.runs[sc.CSR_GRID_CAP * sc.BLOCK:] > 1) + sc.CSR_GRID_CAP * sc.BLOCK
+        assert sorted(case.runs[late].tolist()) == [2, 5] and late.max() == case.n_unique - 1      # (the last entry of the last slice)
+        assert case.slice_width[sc.CSR_GRID_CAP] == 5 and case.slice_width[0] > 8                   # unrolled loop + remainder on both trips
+        assert int((case.runs > 1).sum()) == 3
+        for p in np.flatnonzero(case.runs > 1):
+            t = case.triplets[case.perm].tolist()[case.start[p]: case.start[p + 1]]
+            _sensitivity(t, float(bound[p]))
+    # the mistake: a stride loop that ends after its first trip leaves what lies beyond the cap unwritten
+    dropped = sc.emulate_gather(case, sc.GATHER_CAP_MUTANT)
+    by_bound, by_bits = _caught(case, dropped)
+    assert by_bound and by_bits, "second trip dropped: not caught"
+    bad = sc.failures(dropped, ref, bound)
+    assert bad.min() == sc.CSR_GRID_CAP * sc.BLOCK and len(bad) == case.n_unique - sc.CSR_GRID_CAP * sc.BLOCK
