@@ -563,6 +563,24 @@ int pk_band_record_batch(pk_ctx* ctx, int32_t B, double* rec /* 8 B: entry e at 
 int pk_solve_banded_batch(pk_ctx* ctx, int32_t B, const double* s1 /* B x n */, const double* s2 /* B x m */,
                           const double* b /* B x (n + m) */, double* x /* B x (n + m) */, double* rec /* 8 B */);
 
+/* MANY RIGHT-HAND SIDES AGAINST ONE FACTORISATION (kernels pk_bd_mprep_k, pk_bd_msolve_k, pk_bd_mdot_k, pk_bd_mborder_k,
+ * pk_bd_mxb_k, pk_bd_mscatter_k).  pk_band_solve_multi_dev solves K sol_c = rhs_c for k right-hand sides,
+ * 1 <= k <= 64, with the factors of the last pk_band_factor_dev, in the launches of ONE solve: right-hand side c is the n + m
+ * doubles at d_rhs + c stride_rhs, its solution at d_sol + c stride_sol, both strides at least n + m.  The sweeps take one
+ * workgroup per right-hand side; the border's columns of U are swept once per call and its Schur complement is formed and
+ * factored once.  Column c has, bit for bit, the solution pk_band_solve_dev gives for column c alone, and the record is that
+ * call's record; after a failed factorisation (status != 0) no column of d_sol is written; a column with an entry that is not
+ * finite harms that column only.  Enqueued on the context's stream, not waited for.  pk_solve_banded_multi is the host form on
+ * pk_linearize's values: one upload of b (k rows), s1 and s2, factor, the block solve, one download of x (left untouched unless
+ * status is 0) and the record.
+ * Errors: 110 a null device pointer; 119 a sharded context; 134 k outside 1 ... 64, a stride below n + m, no plan, no
+ * factorisation; 136 no device memory (the message names the array and k); 60 a null host buffer; the host form also 117 and 118
+ * as pk_solve_banded.  Nothing is enqueued or written after a refusal. */
+int pk_band_solve_multi_dev(pk_ctx* ctx, int32_t k, const double* d_rhs, int64_t stride_rhs /* >= n + m */, double* d_sol,
+                            int64_t stride_sol /* >= n + m */);
+int pk_solve_banded_multi(pk_ctx* ctx, int32_t k, const double* s1, const double* s2, const double* b /* k x (n + m) */,
+                          double* x /* k x (n + m) */, double* rec /* 8 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,12 @@
 // permuted numbering or -1; 2 the smallest |pivot| of the band (+inf without one); 3 the largest (0.0 without one); 4 Nb; 5 w;
 // 6 p; 7 the interchanges that moved a row.  After status != 0 sol is left untouched.
 //
+//   block     k <= PK_BD_RHS_CAP right-hand sides against one factorisation in the launches of one solve: R = p + k sweep
+//             vectors (the p columns of U swept once per call), (p + k) p dots, S formed and factored ONCE by thread 0 of the
+//             border workgroup and thread c substituting for column c (the interchanges and multipliers are replayed on its own
+//             t in the order the single form applies them), x_B and the scatter over k (Nb + p) and k (n + m) elements
+//             [pk_bd_mprep_k ... pk_bd_mscatter_k].  Column c has the bits the single solve gives for it alone.
+//
 // Pivoting is confined to the band part: a K whose band part B is singular while K is not fails here (status 1).
 // No atomics, no fused multiply-add, no workgroup waits for another: every dependency is a kernel boundary on the stream.
 #include <cmath>
@@ -85,6 +91,18 @@ struct PkBandBatchArgs {
   PkBandArgs a;
   int64_t s_h, s_j, s_s1, s_s2, s_band, s_U, s_C, s_ipiv, s_work, s_rec, s_partial, s_rhs, s_sol;
 };
+
+// A block of right-hand sides: k <= PK_BD_RHS_CAP of them against ONE factorisation.  `a` holds the system; a.Y has p + k sweep
+// vectors (U's columns, then the k right-hand sides), a.x k slices of nb + p, a.bc k slices of p, a.partial (p + k) p planes.
+// Column c reads a.rhs + c s_rhs and writes a.sol + c s_sol; the scatter reads slice c at from + c s_from.
+enum { PK_BD_RHS_CAP = 64 };
+struct PkBandMultiArgs {
+  PkBandArgs a;
+  const double* from;
+  int64_t s_rhs, s_sol, s_from;
+  int32_t k;
+};
+static_assert(PK_BD_RHS_CAP <= PK_BLOCK, "one thread of the border workgroup per right-hand side");
 
 #ifdef __HIPCC__
 #define BD_BODY __device__ __forceinline__
@@ -457,6 +475,110 @@ BD_BODY void bd_border_body(const PkBandArgs& a, double* s, double* dots, double
   BD_PHASE(bd_border_thread(a, t, dots, S, v));
 }
 
+// ---------------------------------------------------------------- the block of k right-hand sides
+// [Y_0 ... Y_{p-1} | y_b of column 0 ... k - 1] and the k slices of b_C from U and the right-hand sides
+PK_LIB_FN void bd_mprep_element(const PkBandMultiArgs& g, int64_t e) {
+  const PkBandArgs& a = g.a;
+  const int64_t nu = a.nb * a.p, N = a.nb + a.p;
+  if (e < nu) { a.Y[e] = a.U[e]; return; }
+  const int64_t c = (e - nu) / N, k = (e - nu) % N;      // the column and the permuted position
+  const double v = a.rhs[c * g.s_rhs + (a.order ? (int64_t)a.order[k] : k)];
+  if (k < a.nb) a.Y[nu + c * a.nb + k] = v;
+  else a.bc[c * a.p + (k - a.nb)] = v;
+}
+
+PK_LIB_FN void bd_mxb_element(const PkBandMultiArgs& g, int64_t e) {
+  const PkBandArgs& a = g.a;
+  const int64_t c = e / a.nb, i = e % a.nb, N = a.nb + a.p;
+  double v = a.Y[((int64_t)a.p + c) * a.nb + i];
+  for (int q = 0; q < a.p; ++q) {
+    const double pr = a.Y[(int64_t)q * a.nb + i] * a.x[c * N + a.nb + q];
+    v = v - pr;
+  }
+  a.x[c * N + i] = v;
+}
+
+PK_LIB_FN void bd_mscatter_element(const PkBandMultiArgs& g, int64_t e) {
+  const PkBandArgs& a = g.a;
+  const int64_t c = e / a.nsol, i = e % a.nsol;
+  const int64_t k = a.where ? (int64_t)a.where[i] : i;
+  a.sol[c * g.s_sol + i] = k < 0 ? 0.0 : g.from[c * g.s_from + k];
+}
+
+// thread 0: S = C - U^T Y_U and its LU with partial pivoting, ONCE for the block.  The multipliers are kept as they are formed
+// (L[r + k p], never exchanged afterwards) beside the interchanges piv[k], so that a column can replay on its own t exactly
+// what bd_border_thread does to v; piv[p] is 1 after a failed pivot.
+PK_LIB_FN void bd_mborder_factor(const PkBandArgs& a, int t, const double* dots, double* S, double* L, int* piv) {
+  if (t != 0) return;
+  const int p = a.p;
+  piv[p] = 0;
+  for (int c = 0; c < p; ++c)
+    for (int r = 0; r < p; ++r) S[r + c * p] = a.C[r + c * p] - dots[c * p + r];
+  for (int k = 0; k < p; ++k) {
+    int ip = k;
+    double big = -1.0;
+    for (int r = k; r < p; ++r) {
+      const double e = S[r + k * p];
+      const double m = __builtin_isfinite(e) ? __builtin_fabs(e) : __builtin_inf();
+      if (m > big) { big = m; ip = r; }
+    }
+    if (!__builtin_isfinite(big) || big == 0.0) {
+      a.rec[BD_STATUS] = __builtin_isfinite(big) ? 2.0 : 3.0;
+      a.rec[BD_COLUMN] = (double)(a.nb + k);
+      piv[p] = 1;
+      return;
+    }
+    piv[k] = ip;
+    if (ip != k)
+      for (int c = 0; c < p; ++c) { const double u = S[k + c * p]; S[k + c * p] = S[ip + c * p]; S[ip + c * p] = u; }
+    for (int r = k + 1; r < p; ++r) {
+      const double l = S[r + k * p] / S[k + k * p];
+      S[r + k * p] = l;
+      L[r + k * p] = l;
+      for (int c = k + 1; c < p; ++c) { const double pr = l * S[k + c * p]; S[r + c * p] = S[r + c * p] - pr; }
+    }
+  }
+}
+// thread c < k: t = b_C - U^T y_b of column c, the interchanges and multipliers replayed, the back substitution; v is the
+// column's own slice of P_CAP doubles
+PK_LIB_FN void bd_mborder_column(const PkBandMultiArgs& g, int c, const double* dots, const double* S, const double* L, const int* piv,
+                                 double* vs) {
+  const PkBandArgs& a = g.a;
+  const int p = a.p;
+  if (c >= g.k || piv[p] != 0) return;
+  double* v = vs + c * PK_BD_P_CAP;
+  for (int r = 0; r < p; ++r) v[r] = a.bc[(int64_t)c * p + r] - dots[(p + c) * p + r];
+  for (int k = 0; k < p; ++k) {
+    const int ip = piv[k];
+    if (ip != k) { const double u = v[k]; v[k] = v[ip]; v[ip] = u; }
+    for (int r = k + 1; r < p; ++r) {
+      const double pr = L[r + k * p] * v[k];
+      v[r] = v[r] - pr;
+    }
+  }
+  for (int k = p - 1; k >= 0; --k) {
+    double e = v[k];
+    for (int q = k + 1; q < p; ++q) { const double pr = S[k + q * p] * v[q]; e = e - pr; }
+    v[k] = e / S[k + k * p];
+  }
+  for (int k = 0; k < p; ++k) a.x[(int64_t)c * (a.nb + p) + a.nb + k] = v[k];
+}
+
+BD_BODY void bd_mborder_body(const PkBandMultiArgs& g, double* s, double* dots, double* S, double* L, int* piv, double* vs) {
+  const PkBandArgs& a = g.a;
+  if (a.rec[BD_STATUS] != 0.0) return;
+  for (int r = 0; r < a.p + g.k; ++r) {
+    PkBandArgs b = a;
+    b.partial = a.partial + (int64_t)r * a.p * a.n_pieces;
+    b.planes = a.p;
+    BD_PHASE(lib_scalar_thread(b, t, s));
+    BD_TREE(lib_planes_step, s, (int)a.p);
+    BD_PHASE(bd_dots_keep(dots, s, t, r, a.p));
+  }
+  BD_PHASE(bd_mborder_factor(a, t, dots, S, L, piv));
+  BD_PHASE(bd_mborder_column(g, t, dots, S, L, piv, vs));
+}
+
 #ifdef __HIPCC__
 // ---------------------------------------------------------------- kernels (gfx950)
 __global__ void __launch_bounds__(PK_BLOCK) pk_bd_init_k(PkBandArgs a) { bd_init_thread(a, (int)threadIdx.x); }
@@ -635,6 +757,65 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_bd_scatter_bk(PkBandBatchArgs g) 
     hipLaunchKernelGGL(pk_bd_update_bk, dim3((grid), (ny)), dim3(PK_BLOCK), 0, (st), (g), (columns));        \
     PK_HIP((c), hipGetLastError());                                                                          \
   } while (0)
+
+// ---------------------------------------------------------------- the block kernels: k right-hand sides, one factorisation
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mprep_k(PkBandMultiArgs g) {
+  const int64_t len = g.a.nb * g.a.p + (int64_t)g.k * (g.a.nb + g.a.p), items = bd_items(len);
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
+    if (e < len) bd_mprep_element(g, e);
+  }
+}
+
+// work item = a sweep vector: a column of U or a right-hand side
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_msolve_k(PkBandMultiArgs g) {
+  __shared__ double F[PK_BD_CH * BD_LW];
+  __shared__ double ring[PK_BD_RING];
+  __shared__ int ipl[PK_BD_CH];
+  const int64_t R = (int64_t)g.a.p + g.k;
+  for (int64_t q = (int64_t)blockIdx.x; q < R; q += (int64_t)gridDim.x) bd_solve_body(g.a, q, F, ring, ipl);
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mdot_k(PkBandMultiArgs g) {
+  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
+  const PkBandArgs& a = g.a;
+  const int t = (int)threadIdx.x;
+  const int64_t items = ((int64_t)a.p + g.k) * a.n_pieces;
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t r = item / a.n_pieces, pc = item % a.n_pieces;
+    bd_dot_thread(a, r, pc, t, s);
+    __syncthreads();
+    lib_tree(lib_planes_step, s, t, (int)a.p);
+    if (t < a.p) bd_dot_store(a, r, pc, t, s);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mborder_k(PkBandMultiArgs g) {
+  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
+  __shared__ double dots[(PK_BD_P_CAP + PK_BD_RHS_CAP) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], L[PK_BD_P_CAP * PK_BD_P_CAP];
+  __shared__ double vs[PK_BD_RHS_CAP * PK_BD_P_CAP];
+  __shared__ int piv[PK_BD_P_CAP + 1];
+  bd_mborder_body(g, s, dots, S, L, piv, vs);
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mxb_k(PkBandMultiArgs g) {
+  if (g.a.rec[BD_STATUS] != 0.0) return;
+  const int64_t len = (int64_t)g.k * g.a.nb, items = bd_items(len);
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
+    if (e < len) bd_mxb_element(g, e);
+  }
+}
+
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mscatter_k(PkBandMultiArgs g) {
+  if (g.a.rec[BD_STATUS] != 0.0) return;
+  const int64_t len = (int64_t)g.k * g.a.nsol, items = bd_items(len);
+  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
+    const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
+    if (e < len) bd_mscatter_element(g, e);
+  }
+}
 #else
 // ---------------------------------------------------------------- host stand-in: the identical walk
 static void bd_init_host(const PkBandArgs& a, unsigned) { bd_init_thread(a, 0); }
@@ -695,6 +876,41 @@ static void bd_dot_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { 
 static void bd_border_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_border_host(bd_entry(g, y), grid); }
 static void bd_xb_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_xb_host(bd_entry(g, y), grid); }
 static void bd_scatter_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_scatter_host(bd_entry(g, y), grid); }
+// the block kernels' stand-ins
+static void bd_mprep_host(const PkBandMultiArgs& g, unsigned grid) {
+  lib_elements_host(grid, g.a.nb * g.a.p + (int64_t)g.k * (g.a.nb + g.a.p), [&](int64_t e) { bd_mprep_element(g, e); });
+}
+static void bd_msolve_host(const PkBandMultiArgs& g, unsigned grid) {
+  static double F[PK_BD_CH * BD_LW];
+  double ring[PK_BD_RING];
+  int ipl[PK_BD_CH];
+  lib_walk_host(grid, (int64_t)g.a.p + g.k, [&](int64_t q) { bd_solve_body(g.a, q, F, ring, ipl); });
+}
+static void bd_mdot_host(const PkBandMultiArgs& g, unsigned grid) {
+  static double s[PK_BD_P_CAP * PK_BLOCK];
+  const PkBandArgs& a = g.a;
+  lib_walk_host(grid, ((int64_t)a.p + g.k) * a.n_pieces, [&](int64_t item) {
+    const int64_t r = item / a.n_pieces, pc = item % a.n_pieces;
+    for (int t = 0; t < PK_BLOCK; ++t) bd_dot_thread(a, r, pc, t, s);
+    lib_tree_host(lib_planes_step, s, (int)a.p);
+    for (int q = 0; q < a.p; ++q) bd_dot_store(a, r, pc, q, s);
+  });
+}
+static void bd_mborder_host(const PkBandMultiArgs& g, unsigned) {
+  static double s[PK_BD_P_CAP * PK_BLOCK];
+  double dots[(PK_BD_P_CAP + PK_BD_RHS_CAP) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], L[PK_BD_P_CAP * PK_BD_P_CAP];
+  double vs[PK_BD_RHS_CAP * PK_BD_P_CAP];
+  int piv[PK_BD_P_CAP + 1];
+  bd_mborder_body(g, s, dots, S, L, piv, vs);
+}
+static void bd_mxb_host(const PkBandMultiArgs& g, unsigned grid) {
+  if (g.a.rec[BD_STATUS] != 0.0) return;
+  lib_elements_host(grid, (int64_t)g.k * g.a.nb, [&](int64_t e) { bd_mxb_element(g, e); });
+}
+static void bd_mscatter_host(const PkBandMultiArgs& g, unsigned grid) {
+  if (g.a.rec[BD_STATUS] != 0.0) return;
+  lib_elements_host(grid, (int64_t)g.k * g.a.nsol, [&](int64_t e) { bd_mscatter_element(g, e); });
+}
 #define BD_LAUNCH_UPDATE_Y(c, grid, ny, st, g, columns)                                                \
   fake_hip_enqueue((st), [a_ = (g), g_ = (grid), y_ = (unsigned)(ny), n_ = (columns)]() {              \
     for (unsigned y = 0; y < y_; ++y) bd_update_host(bd_entry(a_, y), g_, n_);                         \
@@ -706,6 +922,7 @@ void free_band(pk_ctx* c) {
   release(b.d_map); release(b.d_order); release(b.d_where);
   release(b.d_work); release(b.d_ipiv); release(b.d_partial); release(b.d_scratch); release(b.d_raw);
   release(b.d_bwork); release(b.d_bipiv); release(b.d_bpartial); release(b.d_bscratch); release(b.d_braw);
+  release(b.d_mwork); release(b.d_mpartial); release(b.d_mscratch);
   b = PkBand{};
 }
 
@@ -878,6 +1095,50 @@ int bd_partial_batch(pk_ctx* c, PkBandBatchArgs& g, int32_t B, const char* who) 
   return 0;
 }
 
+// ---------------------------------------------------------------- the block: k right-hand sides behind one factorisation
+// the launches of ONE solve (3 without a border, 6 with one); the arguments hold everything but the scatter's source
+int bd_enqueue_solve_multi(pk_ctx* c, PkBandMultiArgs g, hipStream_t st) {
+  const PkBandArgs& a = g.a;
+  const int64_t k = g.k, N = a.nb + a.p;
+  if (N > 0) PK_LIB_LAUNCH(c, pk_bd_mprep_k, bd_mprep_host, lib_grid(lib_elem_items(a.nb * a.p + k * N)), st, g);
+  if (a.nb > 0) PK_LIB_LAUNCH(c, pk_bd_msolve_k, bd_msolve_host, lib_grid((int64_t)a.p + k), st, g);
+  g.from = a.Y; g.s_from = a.nb;      // (without a border the solutions are the swept right-hand sides themselves)
+  if (a.p > 0) {
+    PK_LIB_LAUNCH(c, pk_bd_mdot_k, bd_mdot_host, lib_grid(((int64_t)a.p + k) * a.n_pieces), st, g);
+    PK_LIB_LAUNCH(c, pk_bd_mborder_k, bd_mborder_host, 1u, st, g);
+    if (a.nb > 0) PK_LIB_LAUNCH(c, pk_bd_mxb_k, bd_mxb_host, lib_grid(lib_elem_items(k * a.nb)), st, g);
+    g.from = a.x; g.s_from = N;
+  }
+  if (a.nsol > 0) PK_LIB_LAUNCH(c, pk_bd_mscatter_k, bd_mscatter_host, lib_grid(lib_elem_items(k * a.nsol)), st, g);
+  return 0;
+}
+
+int bd_rhs_count(pk_ctx* c, int32_t k, const char* who) {
+  if (k < 1 || k > PK_BD_RHS_CAP) return fail(c, 134, "%s: a block of %d right-hand sides (1 ... %d)", who, k, (int)PK_BD_RHS_CAP);
+  return 0;
+}
+
+// the block's work arrays for k right-hand sides of the shape in g.a, and its slices into the arguments
+int bd_multi_work(pk_ctx* c, PkBandMultiArgs& g, const char* who) {
+  PkBandArgs& a = g.a;
+  PkBand& b = c->band;
+  const size_t k = (size_t)g.k, nb = (size_t)a.nb, p = (size_t)a.p;
+  char named[160];
+  std::snprintf(named, sizeof named, "the sweep vectors and solutions of a block of %d right-hand sides", (int)g.k);
+  int rc = lib_reserve(c, b.d_mwork, b.mwork_cap, (p + k) * nb + k * (nb + p) + k * p + 1, 136, who, named);
+  if (rc) return rc;
+  a.n_pieces = lib_dot_pieces(a.nb);
+  if (p > 0) {
+    std::snprintf(named, sizeof named, "the partial sums of a block of %d right-hand sides", (int)g.k);
+    if ((rc = lib_reserve(c, b.d_mpartial, b.mpartial_cap, (p + k) * p * (size_t)a.n_pieces, 136, who, named))) return rc;
+  }
+  a.partial = p > 0 ? b.d_mpartial : nullptr;
+  a.Y = b.d_mwork;
+  a.x = a.Y + (p + k) * nb;
+  a.bc = a.x + k * (nb + p);
+  return 0;
+}
+
 int bd_batch_planned(pk_ctx* c, const char* who) {
   if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
   if (c->band.sources != c->csr[1].n_unique + c->csr[0].n_unique + (int64_t)c->n + c->m)
@@ -966,6 +1227,24 @@ int pk_band_solve_dev(pk_ctx* c, const double* d_rhs, double* d_sol) {
   return bd_enqueue_solve(c, a, c->stream);
 }
 
+int pk_band_solve_multi_dev(pk_ctx* c, int32_t k, const double* d_rhs, int64_t stride_rhs, double* d_sol, int64_t stride_sol) {
+  const char* who = "pk_band_solve_multi";
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!d_rhs || !d_sol) return fail(c, 110, "%s: null device pointer", who);
+  if ((rc = bd_context(c, who)) || (rc = bd_rhs_count(c, k, who))) return rc;
+  if (!c->band.planned || !c->band.factored) return fail(c, 134, "%s: no factorisation (pk_band_plan, pk_band_factor_dev)", who);
+  const int64_t N = (int64_t)c->n + c->m;
+  if ((rc = bd_stride(c, stride_rhs, N, false, who, "the right-hand sides")) || (rc = bd_stride(c, stride_sol, N, false, who, "the solutions")))
+    return rc;
+  PkBandMultiArgs g{};
+  g.a = bd_planned(c);      // (the matrix, ipiv, order, where and the record; the work slices are the block's own)
+  g.k = k; g.s_rhs = stride_rhs; g.s_sol = stride_sol;
+  if ((rc = bd_multi_work(c, g, who))) return rc;
+  g.a.rhs = d_rhs; g.a.sol = d_sol;
+  return bd_enqueue_solve_multi(c, g, c->stream);
+}
+
 int pk_band_record(pk_ctx* c, double* rec) {
   const char* who = "pk_band_record";
   int rc = ready(c);
@@ -996,6 +1275,26 @@ int pk_solve_banded(pk_ctx* c, const double* s1, const double* s2, const double*
   if (N) PK_HIP(c, hipMemcpyAsync(got.data(), d_x, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
   if ((rc = pk_band_record(c, rec))) return rc;      // (synchronises)
   if (rec[BD_STATUS] == 0.0) std::copy(got.begin(), got.begin() + (long)N, x);
+  return 0;
+}
+
+int pk_solve_banded_multi(pk_ctx* c, int32_t k, const double* s1, const double* s2, const double* b, double* x, double* rec) {
+  const char* who = "pk_solve_banded_multi";
+  const double *jvals = nullptr, *hvals = nullptr;
+  int rc = host_ready(c, s1 && s2 && b && x && rec);
+  if (rc || (rc = solve_ops_ready(c, true, true, who)) || (rc = bd_rhs_count(c, k, who))) return rc;
+  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
+  if ((rc = solve_linearized(c, true, jvals, hvals, who))) return rc;
+  const size_t n = (size_t)c->n, m = (size_t)c->m, N = n + m, nk = (size_t)k;
+  if ((rc = lib_reserve(c, c->band.d_mscratch, c->band.mscratch_cap, (2 * nk + 1) * N + 1, 136, who, "host-form scratch of the block"))) return rc;
+  double *d_b = c->band.d_mscratch, *d_s = d_b + N * nk, *d_x = d_s + N;
+  PK_HIP(c, hipSetDevice(c->device));
+  if ((rc = lib_upload(c, d_b, b, N * nk)) || (rc = lib_upload(c, d_s, s1, n)) || (rc = lib_upload(c, d_s + n, s2, m))) return rc;
+  if ((rc = pk_band_factor_dev(c, hvals, jvals, d_s, d_s + n)) || (rc = pk_band_solve_multi_dev(c, k, d_b, (int64_t)N, d_x, (int64_t)N))) return rc;
+  std::vector<double> got(N * nk + 1);
+  if (N) PK_HIP(c, hipMemcpyAsync(got.data(), d_x, sizeof(double) * N * nk, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = pk_band_record(c, rec))) return rc;      // (synchronises)
+  if (rec[BD_STATUS] == 0.0) std::copy(got.begin(), got.begin() + (long)(N * nk), x);
   return 0;
 }
 
@@ -1117,6 +1416,26 @@ int pk_band_raw_dev(pk_ctx* c, int64_t nb, int32_t w, int32_t p, int32_t R, doub
   bd_solve_slices(a, c->band.d_raw);
   if ((rc = bd_enqueue_factor(c, a, false, c->stream))) return rc;
   return bd_enqueue_solve(c, a, c->stream);
+}
+
+int pk_band_raw_multi_dev(pk_ctx* c, int64_t nb, int32_t w, int32_t p, int32_t k, double* d_band, const double* d_U, const double* d_C,
+                          const double* d_rhs, int64_t stride_rhs, int32_t* d_ipiv, double* d_x, int64_t stride_x, double* d_rec) {
+  const char* who = "pk_band_raw_multi";
+  int rc = ready(c);
+  if (rc) return rc;
+  if (!d_band || !d_rhs || !d_ipiv || !d_x || !d_rec || (p > 0 && (!d_U || !d_C))) return fail(c, 110, "%s: null device pointer", who);
+  if ((rc = bd_shape(c, nb, w, p, who)) || (rc = bd_rhs_count(c, k, who))) return rc;
+  if ((rc = bd_stride(c, stride_rhs, nb + p, false, who, "the right-hand sides")) || (rc = bd_stride(c, stride_x, nb + p, false, who, "the solutions")))
+    return rc;
+  PkBandMultiArgs g{};
+  PkBandArgs& a = g.a;
+  a.nb = nb; a.w = w; a.p = p; a.ldab = bd_ldab(w);
+  a.band = d_band; a.U = const_cast<double*>(d_U); a.C = const_cast<double*>(d_C);      // (no fill: the kernels read them only)
+  a.ipiv = d_ipiv; a.rec = d_rec; a.rhs = d_rhs; a.sol = d_x; a.nsol = nb + p;
+  g.k = k; g.s_rhs = stride_rhs; g.s_sol = stride_x;
+  if ((rc = bd_multi_work(c, g, who))) return rc;
+  if ((rc = bd_enqueue_factor(c, a, false, c->stream))) return rc;
+  return bd_enqueue_solve_multi(c, g, c->stream);
 }
 
 int pk_band_raw_batch_dev(pk_ctx* c, int32_t B, int64_t nb, int32_t w, int32_t p, int32_t R, double* d_band, int64_t stride_band,

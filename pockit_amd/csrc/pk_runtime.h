@@ -23,7 +23,8 @@
 //                   pk_sl_update_k, pk_sl_merit_k, pk_sl_scalar_k: the library's own kernels)
 //   pk_band.cpp     the step's system assembled, factored and solved on the device: a band LU with partial pivoting inside the
 //                   band, bordered by the few dense unknowns (pk_bd_init_k, pk_bd_fill_k, pk_bd_panel_k, pk_bd_update_k,
-//                   pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k: the library's own kernels)
+//                   pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k, their batch forms pk_bd_*_bk and
+//                   the block solve's pk_bd_mprep_k ... pk_bd_mscatter_k: the library's own kernels)
 //   pk_solve.cpp    the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp: the context's growing
 //                   arrays (lib_reserve, also pk_merit.cpp's, pk_ipm.cpp's, pk_slack.cpp's and pk_band.cpp's), the common checks, the skeletons of record / advance / the host loop
 //   pk_error.cpp    fail(): where an error message is kept
@@ -254,6 +255,14 @@ struct PkBand {
   double* d_braw = nullptr;         // pk_band_raw_batch_dev's B x [Y | x | b_C]
   size_t braw_cap = 0;
   int32_t batch = 0;                // the entries of the last batch factorisation (0: none)
+  // the block solve (pk_band_solve_multi_dev ...): k right-hand sides against one factorisation, reserved by the first call,
+  // grown by a larger k, released with the plan
+  double* d_mwork = nullptr;        // [Y: p + k sweep vectors of Nb | x: k slices of Nb + p | b_C: k slices of p]
+  size_t mwork_cap = 0;
+  double* d_mpartial = nullptr;     // the partial sums of the (p + k) p dots
+  size_t mpartial_cap = 0;
+  double* d_mscratch = nullptr;     // the host block form's [b (k rows) | s1 s2 | x (k rows)]
+  size_t mscratch_cap = 0;
 };
 
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)

@@ -263,6 +263,12 @@ int pk_band_raw_dev(pk_ctx* ctx, int64_t nb, int32_t w, int32_t p, int32_t R, do
 int pk_band_raw_batch_dev(pk_ctx* ctx, int32_t B, int64_t nb, int32_t w, int32_t p, int32_t R, double* d_band, int64_t stride_band,
                           const double* d_U, int64_t stride_U, const double* d_C, int64_t stride_C, const double* d_rhs, int64_t stride_rhs,
                           int32_t* d_ipiv, int64_t stride_ipiv, double* d_x, int64_t stride_x, double* d_rec, int64_t stride_rec);
+/* pk_band_raw_dev with k right-hand sides (1 <= k <= 64) in place of R == p + 1: one factorisation of the caller's matrix, then
+ * the block solve of pk_band_solve_multi_dev.  Right-hand side c is the nb + p values at d_rhs + c stride_rhs in permuted order,
+ * its solution at d_x + c stride_x (both strides at least nb + p); one d_ipiv, one record.  Column c gets the bits pk_band_raw_dev
+ * gives for it alone.  Errors 110, 134, 136. */
+int pk_band_raw_multi_dev(pk_ctx* ctx, int64_t nb, int32_t w, int32_t p, int32_t k, double* d_band, const double* d_U, const double* d_C,
+                          const double* d_rhs, int64_t stride_rhs, int32_t* d_ipiv, double* d_x, int64_t stride_x, double* d_rec);
 
 #ifdef __cplusplus
 }

@@ -1413,6 +1413,16 @@ class Evaluator:
         variables get 0.0).  Not waited for; after a failed factorisation ``d_sol`` is left untouched."""
         self.ctx.check(self.ctx.lib.pk_band_solve_dev(self.ctx.handle, d_rhs, d_sol))
 
+    def band_solve_multi_dev(self, k, d_rhs, d_sol, stride_rhs=None, stride_sol=None):
+        """Enqueue the k solves ``K sol_c = rhs_c`` (1 ... 64) with the factors of ``band_factor_dev`` in the launches of ONE
+        solve: right-hand side c is the n + m doubles ``stride_rhs`` c behind ``d_rhs``, its solution ``stride_sol`` c behind
+        ``d_sol`` (None: n + m; at least n + m).  Column c has the bits ``band_solve_dev`` gives for it alone; the record is
+        ``band_record``'s.  Not waited for; after a failed factorisation no column of ``d_sol`` is written."""
+        size = self.plan.n + self.plan.m
+        stride_rhs = size if stride_rhs is None else stride_rhs
+        stride_sol = size if stride_sol is None else stride_sol
+        self.ctx.check(self.ctx.lib.pk_band_solve_multi_dev(self.ctx.handle, int(k), d_rhs, int(stride_rhs), d_sol, int(stride_sol)))
+
     def band_record(self):
         """The record of the last factorisation and solve (8 doubles: status, failing column, smallest and largest |pivot|,
         Nb, w, p, interchanges), waited for."""
@@ -2125,6 +2135,58 @@ class Linearization:
         dp = runtime.as_dp
         ev.ctx.check(ev.ctx.lib.pk_solve_banded_batch(ev.ctx.handle, B, dp(s1), dp(s2), dp(b), dp(X), dp(rec)))
         return X, [BandInfo(rec[e], X[e], self.n) for e in range(B)]
+
+    MULTI_CAP = 64      # PK_BD_RHS_CAP: the right-hand sides of one block solve
+
+    def solve_banded_multi(self, B, s1=None, s2=None):
+        """``solve_banded`` for k right-hand sides against ONE factorisation: ``B`` of shape ``(k, n + m)``, any k >= 1, ``s1``
+        and ``s2`` as ``solve_banded`` takes them (one matrix).  Up to 64 right-hand sides are one call -- one upload, the
+        factorisation, a block solve in the launches of one solve, one download; beyond that the rows are served in chunks of
+        64 against the same factors.  Returns ``(X, info)``: ``X`` of shape ``(k, n + m)``, row c with the bits
+        ``solve_banded(B[c], s1, s2)`` returns, all NaN unless ``info.status == "solved"``; ``info`` a ``BandInfo`` (on row
+        0).  The ordering and its ``ValueError``s are ``solve_banded``'s."""
+        from .band import BandOrdering
+
+        ev, _, s1, s2 = self._kkt_args(s1, s2, True)
+        size = self.n + self.m
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[1] != size or B.shape[0] < 1:
+            raise ValueError(f"B must have shape (k, {size}) with k >= 1")
+        k = B.shape[0]
+        s1 = np.zeros(self.n) if s1 is None else s1
+        s2 = np.zeros(self.m) if s2 is None else s2
+        free = np.asarray(ev.plan.v_lb, dtype=np.float64) != np.asarray(ev.plan.v_ub, dtype=np.float64)
+        ordering = BandOrdering(ev.csr_map("jac"), ev.csr_map("hess"), free)
+        ev.band_plan(ordering)
+        X, rec = np.full((k, size), np.nan), np.empty(8)
+        dp = runtime.as_dp
+        first = min(k, self.MULTI_CAP)
+        head = np.full((first, size), np.nan)
+        ev.ctx.check(ev.ctx.lib.pk_solve_banded_multi(ev.ctx.handle, first, dp(s1), dp(s2), dp(np.ascontiguousarray(B[:first])), dp(head), dp(rec)))
+        X[:first] = head
+        if k > first and rec[0] == 0.0:      # the later chunks go against the factors that call left, through device arrays of the context
+            lib, h = ev.ctx.lib, ev.ctx.handle
+            nbytes = 8 * self.MULTI_CAP * max(size, 1)
+            d_b, d_x = C.c_void_p(), C.c_void_p()
+            ev.ctx.check(lib.pk_device_alloc(h, nbytes, 0, C.byref(d_b)))
+            try:
+                ev.ctx.check(lib.pk_device_alloc(h, nbytes, 0, C.byref(d_x)))
+                for lo in range(first, k, self.MULTI_CAP):
+                    rows = min(self.MULTI_CAP, k - lo)
+                    chunk, out = np.ascontiguousarray(B[lo: lo + rows]), np.empty((rows, size))
+                    if size:
+                        ev.ctx.check(lib.pk_copy_dev(h, d_b.value, chunk.ctypes.data, chunk.nbytes, None))
+                    ev.band_solve_multi_dev(rows, d_b.value, d_x.value, stride_rhs=size, stride_sol=size)
+                    if size:
+                        ev.ctx.check(lib.pk_copy_dev(h, out.ctypes.data, d_x.value, out.nbytes, None))
+                    ev.sync()
+                    X[lo: lo + rows] = out
+                rec = ev.band_record()
+            finally:
+                for ptr in (d_b, d_x):
+                    if ptr.value:
+                        lib.pk_device_free(h, ptr.value)
+        return X, BandInfo(rec, X[0], self.n)
 
     # ---- the dual side of optimality, and the first block of the KKT right-hand side (csrc/pk_ipm.cpp)
     def dual_residual(self, grad, lam, z=None, negate=False):

@@ -55,7 +55,17 @@ right-hand side in the launches of one, the k records come down in one transfer,
 schedule's order with the same curvature test; the first that passes is the step.  Every entry of a batch has the bits of the
 single factorisation, so the iterates, the iteration count and ``regularisations`` do not depend on k.  What it costs: up to
 k - 1 factorisations and solves nobody needed (the candidates behind the accepted one), and k bands of device memory instead of
-one.  1, the default, is the path without a batch."""
+one.  1, the default, is the path without a batch.
+
+``sensitivity``.  A converged solve already holds the matrix that says how the solution moves with a
+parameter: ``K = [[H + Sigma_x, J^T], [J, -S2]]`` at ``delta_w = 0``.  A parameter is the value of a variable that equal bounds
+hold (a static parameter fixed by ``v_lb == v_ub``: it has a column in J and H though it is out of the system) or the right-hand
+side ``c_i`` of an equality row.  At status 0 K is factored once more at the final iterate, with ``Sigma_x`` and ``S2`` of the last
+measurement, and one column per parameter is solved: ``-[H_sym[:, j]; J[:, j]]`` over the free rows for variable j,
+``[0; e_i]`` for row i.  ``"banded"`` solves all columns in the launches of one solve (``band_solve_multi_dev``, 64 columns per
+call) and downloads ``dx``, ``dlam`` and the record; ``"direct"`` uses one ``splu`` on the downloaded values.  The numbers are
+those of the BARRIER system at the final mu: they equal the active-set sensitivities up to O(mu) under strict complementarity.
+Sensitivities of the bound multipliers and of the slacks are not returned; inequality rows and bounds are not parameters."""
 from __future__ import annotations
 
 import math
@@ -260,6 +270,19 @@ class DirectKkt:
         dx[self.free] = y[: self.nf]
         return dx, y[self.nf:]
 
+    def solve_block(self, hvals, jvals, s1, s2, rhs):
+        """``solve`` for the k rows of ``rhs`` (k, n + m) against ONE factorisation: ``(dx (k, n), dlam (k, m))``."""
+        import scipy.sparse as sp
+        from scipy.sparse.linalg import splu
+
+        data = self.select @ np.concatenate((hvals, jvals, s1, s2))
+        K = sp.csc_matrix((data, self.indices, self.indptr), shape=(self.N, self.N))
+        b = np.concatenate((rhs[:, : self.n][:, self.free], rhs[:, self.n:]), axis=1)
+        y = splu(K).solve(np.asfortranarray(b.T)).T
+        dx = np.zeros((len(rhs), self.n))
+        dx[:, self.free] = y[:, : self.nf]
+        return dx, np.ascontiguousarray(y[:, self.nf:])
+
 
 # ---------------------------------------------------------------------------- the resident iterate and the loop
 class _Resident:
@@ -378,7 +401,130 @@ def _errors(q, m):
     return e_0, e_mu, (bad > 0.0 or not finite)
 
 
-def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band_attempts=1):
+SENSITIVITY_ROUTE = ("a slot whose value the transcription dictates has no column in J or H and cannot be a parameter: make the value a "
+                     "FUNC of a static parameter and fix that parameter by equal bounds")
+
+
+def sensitivity_parameters(system, sensitivity, linear_solver):
+    """The parameters ``solve(..., sensitivity=...)`` asks for as a list of ``("variable", slot)`` and ``("row", row)``, or None;
+    every ``ValueError`` of the argument is raised here, from the plan alone (no device needed)."""
+    if sensitivity is None:
+        return None
+    if linear_solver == "minres":
+        raise ValueError('sensitivity needs linear_solver="direct" or "banded": the "minres" path has no factorisation to reuse')
+    plan = system.plan
+    n, m = plan.n, plan.m
+    fixed = np.asarray(plan.v_lb, dtype=np.float64) == np.asarray(plan.v_ub, dtype=np.float64)
+    equality = np.asarray(plan.c_lb, dtype=np.float64) == np.asarray(plan.c_ub, dtype=np.float64)
+    fixed_at, _, func = dictated_slots(system)
+    dictated = set(int(j) for j in fixed_at) | set(int(slot) for slot, _, _ in func)
+    if isinstance(sensitivity, str):
+        if sensitivity != "fixed":
+            raise ValueError('sensitivity must be None, "fixed" or a mapping with "variables" and "rows"')
+        used = np.zeros(n, dtype=bool)
+        for index in (plan.jac_col, plan.hess_row, plan.hess_col):
+            used[np.asarray(index, dtype=np.int64)] = True
+        return [("variable", int(j)) for j in np.flatnonzero(fixed & used) if int(j) not in dictated]
+    try:
+        unknown = set(sensitivity) - {"variables", "rows"}
+        variables, rows = list(sensitivity.get("variables", ())), list(sensitivity.get("rows", ()))
+    except (TypeError, AttributeError):
+        raise ValueError('sensitivity must be None, "fixed" or a mapping with "variables" and "rows"') from None
+    if unknown:
+        raise ValueError(f'sensitivity: unknown keys {sorted(unknown)} (known: "variables", "rows")')
+    out = []
+    for j in variables:
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not 0 <= j < n:
+            raise ValueError(f"sensitivity: variable {j!r} is not an NLP slot in 0 ... {n - 1}")
+        if int(j) in dictated:
+            raise ValueError(f"sensitivity: variable {int(j)}: {SENSITIVITY_ROUTE}")
+        if not fixed[j]:
+            raise ValueError(f"sensitivity: variable {int(j)} is free (v_lb != v_ub): only a variable held by equal bounds is a parameter")
+        out.append(("variable", int(j)))
+    for i in rows:
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < m:
+            raise ValueError(f"sensitivity: row {i!r} is not a constraint row in 0 ... {m - 1}")
+        if not equality[i]:
+            raise ValueError(f"sensitivity: row {int(i)} is an inequality row (c_lb != c_ub): only the right-hand side of an equality row is a parameter")
+        out.append(("row", int(i)))
+    return out
+
+
+SENSITIVITY_CHUNK = 64       # the right-hand sides of one band_solve_multi_dev
+
+
+def _sensitivities(R, params, direct, status):
+    """``info["sensitivity"]`` at the final iterate of ``R`` (``R.sig_x``, ``R.s2``, ``R.cj``, ``R.ch`` of the last measurement
+    and evaluation): K at ``delta_w = 0`` factored once, one column per parameter."""
+    out = {"parameters": list(params), "dx": None, "dlam": None, "dobj": None, "status": "not_converged", "record": None}
+    if status != 0:
+        return out
+    ev, at, torch, n, m = R.ev, R.at, R.torch, R.n, R.m
+    N, k = n + m, len(params)
+    var_cols = [(c, j) for c, (kind, j) in enumerate(params) if kind == "variable"]
+    row_cols = [(c, i) for c, (kind, i) in enumerate(params) if kind == "row"]
+    # ---- dobj of a variable: grad f_j + (J^T lam)_j, the k picked entries alone come down
+    dobj = np.zeros(k)
+    R.to_kernels()
+    ev.apply_operator_dev("JT", at(R.cj), at(R.lam), at(R.w))
+    R.to_torch()
+    if var_cols:
+        pick = torch.tensor([j for _, j in var_cols], dtype=torch.int64, device=R.dev)
+        dobj[[c for c, _ in var_cols]] = R.down((R.grad[:n] + R.w[:n])[pick])
+    if row_cols:
+        pick = torch.tensor([i for _, i in row_cols], dtype=torch.int64, device=R.dev)
+        dobj[[c for c, _ in row_cols]] = -R.down(R.lam[:m][pick])
+    out["dobj"] = dobj
+    dx, dlam, record = np.zeros((k, n)), np.zeros((k, m)), None
+    if k and direct is not None:
+        import scipy.sparse as sp
+
+        hvals, jvals, sig_x, s2 = (R.down(t, c).copy() for t, c in ((R.ch, R.map_h.nnz), (R.cj, R.map_j.nnz), (R.sig_x, n), (R.s2, m)))
+        hs = R.map_h.symmetric()
+        H = sp.csc_matrix(sp.csr_matrix((hvals[hs.src], hs.indices, hs.indptr), shape=(n, n)))
+        J = sp.csc_matrix(sp.csr_matrix((jvals, R.map_j.indices, R.map_j.indptr), shape=(m, n)))
+        rhs = np.zeros((k, N))
+        for c, j in var_cols:
+            rhs[c, :n], rhs[c, n:] = -H[:, [j]].toarray()[:, 0], -J[:, [j]].toarray()[:, 0]
+        for c, i in row_cols:
+            rhs[c, n + i] = 1.0
+        try:
+            dx, dlam = direct.solve_block(hvals, jvals, sig_x, s2, rhs)
+        except RuntimeError:
+            dx = None
+    elif k:
+        V = torch.zeros((k, max(N, 1)), dtype=torch.float64, device=R.dev)
+        rhs, sol = torch.zeros_like(V), torch.zeros_like(V)
+        for c, j in var_cols:
+            V[c, j] = -1.0
+        for c, i in row_cols:
+            rhs[c, n + i] = 1.0
+        R.to_kernels()
+        for c, _ in var_cols:      # -[H_sym[:, j]; J[:, j]] = K (-e_j) with s1 = s2 = NULL; the gather drops the fixed rows
+            ev.kkt_apply_dev(at(R.cj), at(V[c]), at(rhs[c]), d_hvals=at(R.ch))
+        ev.band_factor_dev(at(R.ch), at(R.cj), at(R.sig_x), at(R.s2))
+        stride = max(N, 1)
+        for lo in range(0, k, SENSITIVITY_CHUNK):
+            ev.band_solve_multi_dev(min(SENSITIVITY_CHUNK, k - lo), at(rhs[lo]), at(sol[lo]), stride_rhs=stride, stride_sol=stride)
+        record = ev.band_record()
+        R.to_torch()
+        if record[0] == 0.0:
+            S = R.down(sol.reshape(-1), k * stride).reshape(k, stride)
+            dx, dlam = S[:, :n].copy(), S[:, n: n + m].copy()
+        else:
+            dx = None
+    out["record"] = record
+    if dx is None or not (np.all(np.isfinite(dx)) and np.all(np.isfinite(dlam))):
+        out["status"] = "singular"
+        out["dobj"] = None
+        return out
+    for c, j in var_cols:
+        dx[c, j] = 1.0          # (the parameter itself; every other fixed variable stays 0.0)
+    out.update(dx=np.ascontiguousarray(dx.T), dlam=np.ascontiguousarray(dlam.T), status="ok")
+    return out
+
+
+def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band_attempts=1, sensitivity=None):
     """Solve the NLP of ``system`` from ``guess`` (the shapes of ``ipopt.solve``); returns ``(solution, info)``.  ``info`` has
     cyipopt's keys ``x, g, obj_val, mult_g, mult_x_L, mult_x_U, status, status_msg`` and ``iterations``, ``mu``, ``error`` (the
     final E_0), ``linear_iterations`` (MINRES iterations in all; 0 on the direct and banded paths), ``regularisations``, and the slacks with
@@ -387,7 +533,19 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
     ``mu_init`` (0.1), ``print_level`` (0; 1 prints a line per iteration, 2 the step's figures as well, 3 every trial point).  ``linear_solver``: "direct", "minres" or
     "banded" (module docstring: where the latter two work); with "banded" a ``ValueError`` of the ordering (band too wide, border
     too large) leaves the choice of "direct" to the caller.  ``band_attempts`` (1 ... 8, "banded" only): how many ``delta_w`` of the
-    regularisation schedule are factored and solved together (module docstring); the iterates do not depend on it."""
+    regularisation schedule are factored and solved together (module docstring); the iterates do not depend on it.
+
+    ``sensitivity`` (with "direct" or "banded"): None, ``"fixed"`` -- every variable that equal bounds hold, that is not a slot the
+    transcription dictates and that has a non-empty column in J or H -- or a mapping ``{"variables": [NLP slots], "rows":
+    [constraint rows]}`` of variables held by equal bounds and of equality rows.  Then ``info["sensitivity"]`` is a dict:
+    ``parameters`` (``("variable", slot)`` / ``("row", row)`` in column order), ``dx`` (n x k: the derivative of the solution with
+    respect to the variable's value or the row's right-hand side; row j of a variable's own column is 1, other fixed rows 0),
+    ``dlam`` (m x k), ``dobj`` (k: ``grad f_j + (J^T lam)_j`` for a variable, ``-lam_i`` for a row), ``status`` -- ``"ok"``,
+    ``"not_converged"`` (the solve did not end with status 0) or ``"singular"`` (the factorisation at ``delta_w = 0`` failed); the
+    arrays are None unless ``"ok"`` -- and ``record`` (the band record, None on the direct path).  The numbers are those of the
+    barrier system at the final mu: they equal the active-set sensitivities up to O(mu) under strict complementarity.  Bound-
+    multiplier and slack sensitivities are not returned.  ``ValueError`` before any device work: "minres", a free variable, a
+    dictated slot (route: a FUNC of a static parameter fixed by bounds), an inequality row, an index out of range."""
     if linear_solver not in ("direct", "minres", "banded"):
         raise ValueError('linear_solver must be "direct", "minres" or "banded"')
     if isinstance(band_attempts, bool) or not isinstance(band_attempts, (int, np.integer)) or not 1 <= band_attempts <= MAX_BAND_ATTEMPTS:
@@ -396,15 +554,16 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
         raise ValueError('band_attempts other than 1 needs linear_solver="banded"')
     band_attempts = int(band_attempts)
     opt = options(optimizer_options)
+    params = sensitivity_parameters(system, sensitivity, linear_solver)
     x0, bare, _ = preprocess(system, guess, None)
     R = _Resident(system, x0)
     try:
-        return _iterate(system, R, opt, bare, linear_solver, band_attempts)
+        return _iterate(system, R, opt, bare, linear_solver, band_attempts, params)
     finally:
         R.ev.set_bounds()            # the plan's bounds again: a later merit_scan measures against them, not against the fixed slots
 
 
-def _iterate(system, R, opt, bare, linear_solver, band_attempts):
+def _iterate(system, R, opt, bare, linear_solver, band_attempts, params=None):
     """The loop of ``solve`` on the resident iterate ``R``."""
     ev, at, torch, n, m = R.ev, R.at, R.torch, R.n, R.m
     tol, mu = opt["tol"], opt["mu_init"]
@@ -602,10 +761,14 @@ def _iterate(system, R, opt, bare, linear_solver, band_attempts):
         iterations += 1
         R.evaluate()
     R.to_torch()
+    sens = None if params is None else _sensitivities(R, params, direct, status)
+    R.to_torch()
     x = R.down(R.x, n).copy()
     info = make_info(status, x=x, g=R.down(R.g, m).copy(), obj_val=float(R.down(R.f)[0]), mult_g=R.down(R.lam, m).copy(),
                      mult_x_L=R.down(R.zl, n).copy(), mult_x_U=R.down(R.zu, n).copy(), iterations=iterations, mu=mu, error=float(e_0),
                      linear_iterations=linear_iterations, regularisations=reg.count, slack=R.down(R.s, m).copy(),
                      mult_s_L=R.down(R.yl, m).copy(), mult_s_U=R.down(R.yu, m).copy())
+    if sens is not None:
+        info["sensitivity"] = sens
     ev._invalidate_x()
     return postprocess(system, x, bare), info

@@ -8,6 +8,8 @@ on downloaded vectors -- what a caller writes without the units.  Needs an MI355
 sizes, and the host-landed time of one factorisation and of one solve of the band LU with their launches (``--append`` adds the
 rows to ``--out`` instead of replacing it).  ``--banded-batch`` runs the rows of section 24: the batch forms of the band LU at
 B = 1, 2, 4, 8 against B single factorisations and solves in a row, and whole solves with ``band_attempts`` = 1, 2, 4.
+``--multi`` runs the rows of section 27: after one factorisation one block solve at k = 1, 8, 64 against k calls of
+``band_solve_dev``, and a whole solve of the parametrised LQR with ``sensitivity="fixed"`` against the same solve without it.
 """
 import argparse
 import importlib
@@ -222,8 +224,74 @@ def banded_batch_rows(args, models, ipm):
     return lines
 
 
+def multi_rows(args, models, ipm):
+    """after one factorisation, one block solve of k right-hand sides against k single solves in a row
+    (enqueue and wait, host-landed, alternating), then a whole solve with ``sensitivity="fixed"`` against one without."""
+    from pockit_amd.band import BandOrdering
+
+    lines = [f"ip_solve_probe --multi: band_solve_multi_dev (k right-hand sides, the launches of one solve) against k calls of band_solve_dev after one "
+             f"factorisation; median [min, max] of {args.runs} runs each, alternating, host-landed (perf_counter around enqueue + wait)"]
+    for name, scheme, mesh, num_point in reversed(MODELS):
+        ns = importlib.import_module(f"pockit_amd.{scheme}")
+        system, _, guess = getattr(models, name)(ns, mesh, num_point)
+        R = ipm._Resident(system, ipm.preprocess(system, guess, None)[0])
+        R.evaluate()
+        R.to_torch()
+        o = BandOrdering(R.map_j, R.map_h, R.free)
+        R.ev.band_plan(o)
+        n, m, torch = R.n, R.m, R.torch
+        lines.append(f"{name}({scheme}, {mesh}, {num_point}): n {n}, m {m}, Nb {o.nb}, w {o.w}, p {o.p}")
+        R.s1 = R.up(np.ones(n))
+        R.s2 = R.up(np.where(R.ineq, 1.0, 0.0))
+        rhs = torch.from_numpy(np.random.default_rng(3).standard_normal((64, n + m))).to(R.dev)
+        R.to_kernels()
+        at, ev = R.at, R.ev
+        ev.band_factor_dev(at(R.ch), at(R.cj), at(R.s1), at(R.s2))
+        ev.sync()
+        for k in (1, 8, 64):
+            sol, one = torch.zeros((k, n + m), dtype=torch.float64, device=R.dev), torch.zeros((k, n + m), dtype=torch.float64, device=R.dev)
+            R.to_kernels()
+            t_block, t_singles = [], []
+            for _ in range(args.runs + 1):
+                t0 = time.perf_counter()
+                ev.band_solve_multi_dev(k, at(rhs), at(sol))
+                ev.sync()
+                t1 = time.perf_counter()
+                for c in range(k):
+                    ev.band_solve_dev(at(rhs[c]), at(one[c]))
+                ev.sync()
+                t_block.append(t1 - t0)
+                t_singles.append(time.perf_counter() - t1)
+            R.to_torch()
+            same = bool(torch.equal(sol, one))
+            ratio = statistics.median(t_block[1:]) / statistics.median(t_singles[1:])
+            lines.append(f"    k {k:2d}: block {spread(t_block[1:], 1e3, '9.3f')} ms ({o.p + k} workgroups in the sweeps), {k} singles in a row (one wait) "
+                         f"{spread(t_singles[1:], 1e3, '9.3f')} ms, ratio {ratio:.3f}, block / one single {statistics.median(t_block[1:]) * k / statistics.median(t_singles[1:]):.2f}; "
+                         f"bit-equal: {same}; status {int(ev.band_record()[0])}")
+        system.evaluator.close()
+    import sensitivity_models as sm
+
+    for solver in ("banded", "direct"):
+        ns = importlib.import_module("pockit_amd.radau")
+        system, _, guess = sm.param_lqr(ns, 200, 8, 1.0)
+        times, infos = {None: [], "fixed": []}, {}
+        ipm.solve(system, guess, linear_solver=solver)                         # warm-up
+        for _ in range(args.runs):
+            for sens in (None, "fixed"):
+                t0 = time.perf_counter()
+                _, infos[sens] = ipm.solve(system, guess, linear_solver=solver, sensitivity=sens)
+                times[sens].append(time.perf_counter() - t0)
+        s = infos["fixed"]["sensitivity"]
+        lines.append(f"param_lqr(radau, 200, 8), {solver}: n {system.plan.n}, m {system.plan.m}; without sensitivity {spread(times[None], 1e3)} ms, with "
+                     f"sensitivity=\"fixed\" ({len(s['parameters'])} parameter) {spread(times['fixed'], 1e3)} ms; {infos['fixed']['iterations']} iterations, "
+                     f"status {s['status']}, dobj {s['dobj'][0]:.10f}, 2 f {2 * infos['fixed']['obj_val']:.10f}")
+        system.evaluator.close()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--multi", action="store_true", help="the rows of the block solve and the sensitivities instead (DESIGN.md section 27)")
     ap.add_argument("--banded-batch", action="store_true", help="the rows of the batched band LU instead (DESIGN.md section 24)")
     ap.add_argument("--banded", action="store_true", help="the rows of the banded step solver instead (DESIGN.md section 23)")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
@@ -237,8 +305,8 @@ def main():
     from pockit_amd.optimizer import interior_point as ipm
     from pockit_amd.optimizer import scipy as scipy_solver
 
-    if args.banded or args.banded_batch:
-        text = "\n".join((banded_batch_rows if args.banded_batch else banded_rows)(args, models, ipm)) + "\n"
+    if args.banded or args.banded_batch or args.multi:
+        text = "\n".join((multi_rows if args.multi else banded_batch_rows if args.banded_batch else banded_rows)(args, models, ipm)) + "\n"
         print(text, end="")
         if args.out:
             with open(args.out, "a" if args.append else "w") as fh:
