@@ -513,10 +513,10 @@ int pk_slack_update(pk_ctx* ctx, int which, double* v, const double* dv, double*
                     double kappa, double* out /* 4 */);
 
 /* THE STEP'S SYSTEM FACTORED ON THE DEVICE: A BORDERED BAND LU (kernels pk_bd_init_k, pk_bd_fill_k, pk_bd_panel_k, pk_bd_update_k,
- * pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k of the library; pk_band.cpp, DESIGN.md
- * section 23).  K = [[H + diag(s1), J^T], [J, -diag(s2)]] over the free variables and all rows, permuted to [[B, U], [U^T, C]]:
- * B (nb x nb) with half-bandwidth w in LAPACK's dgbtrf storage (kl = ku = w, leading dimension 3 w + 1), U nb x p and C p x p
- * column-major, w <= 192, p <= 8.
+ * pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k of the library: one family that also serves
+ * the batch and the block forms below; pk_band.cpp, DESIGN.md sections 23 and 28).  K = [[H + diag(s1), J^T], [J, -diag(s2)]]
+ * over the free variables and all rows, permuted to [[B, U], [U^T, C]]: B (nb x nb) with half-bandwidth w in LAPACK's dgbtrf
+ * storage (kl = ku = w, leading dimension 3 w + 1), U nb x p and C p x p column-major, w <= 192, p <= 8.
  * pk_band_plan uploads the plan once (it replaces an earlier one): order[k], k < nb + p, is the position in the caller's vectors
  * of n + m values of the unknown at permuted position k (the border last); map holds two source codes per stored slot of
  * [band | U | C] (0: none, +(e + 1): plus entry e of [hvals | jvals | s1 (n) | s2 (m)], -(e + 1): minus it; a slot is 0.0 plus its
@@ -539,18 +539,18 @@ int pk_band_solve_dev(pk_ctx* ctx, const double* d_rhs, double* d_sol);
 int pk_band_record(pk_ctx* ctx, double* rec /* 8 */);
 int pk_solve_banded(pk_ctx* ctx, const double* s1, const double* s2, const double* b, double* x, double* rec /* 8 */);
 
-/* A BATCH OF STEP SYSTEMS BEHIND ONE PLAN (kernels pk_bd_init_bk ... pk_bd_scatter_bk: the same bodies, the entry from the grid's
- * second dimension).  B systems, 1 <= B <= 16, share pk_band_plan's ordering, w, p and assembly map; each
+/* A BATCH OF STEP SYSTEMS BEHIND ONE PLAN (the same ten kernels pk_bd_init_k ... pk_bd_scatter_k: the entry from the grid's second
+ * dimension; DESIGN.md sections 24 and 28).  B systems, 1 <= B <= 16, share pk_band_plan's ordering, w, p and assembly map; each
  * has its own values.  Entry e is assembled, factored and solved exactly as the single forms do it: its solution and its record
  * are, bit for bit, those of pk_band_factor_dev / pk_band_solve_dev on entry e's inputs alone.  A batch costs the launches of one
- * system, each with B times the workgroups.  Strides are in doubles: entry e of an array begins e strides behind entry 0.  A source
- * stride of 0 means that all entries read the same array; otherwise it is at least the array's length (hvals and jvals: the CSR
- * value counts, s1: n, s2: m, rhs and sol: n + m).  An entry that fails (status != 0) does not stop the others: its slice of sol
- * is left untouched, theirs are complete.  The batch has its own arrays, reserved by the first call and grown by a larger B: a
+ * system, each with B times the workgroups.  Strides are in doubles: entry e of an array begins e strides behind entry 0.  A
+ * source stride of 0 means that all entries read the same array; otherwise it is at least the array's length (hvals and jvals: the
+ * CSR value counts, s1: n, s2: m, rhs and sol: n + m).  An entry that fails (status != 0) does not stop the others: its slice of
+ * sol is left untouched, theirs are complete.  The batch has its own arrays, reserved by the first call and grown by a larger B: a
  * batch call leaves the factors of pk_band_factor_dev in place and the other way round; a new plan invalidates both.
  * pk_band_solve_batch_dev and pk_band_record_batch take the B of the last pk_band_factor_batch_dev; the record of entry e is at
- * rec + 8 e.  pk_solve_banded_batch is the host form on pk_linearize's values (J and H shared by the entries): one upload of
- * b, s1, s2 (B rows each), one download of x and the records; the rows of x whose entry failed are left as the caller gave them.
+ * rec + 8 e.  pk_solve_banded_batch is the host form on pk_linearize's values (J and H shared by the entries): one upload of b,
+ * s1, s2 (B rows each), one download of x and the records; the rows of x whose entry failed are left as the caller gave them.
  * Errors: 134 B outside 1 ... 16, a stride that is neither 0 nor at least the length, an output stride below the length, no
  * plan, CSR maps changed since the plan, a solve or a record without a batch factorisation of that B; 110 a null device pointer;
  * 60 a null host buffer; 119 a sharded context; 136 no device memory (the message names the array and B); the host form also 117
@@ -563,8 +563,9 @@ int pk_band_record_batch(pk_ctx* ctx, int32_t B, double* rec /* 8 B: entry e at 
 int pk_solve_banded_batch(pk_ctx* ctx, int32_t B, const double* s1 /* B x n */, const double* s2 /* B x m */,
                           const double* b /* B x (n + m) */, double* x /* B x (n + m) */, double* rec /* 8 B */);
 
-/* MANY RIGHT-HAND SIDES AGAINST ONE FACTORISATION (kernels pk_bd_mprep_k, pk_bd_msolve_k, pk_bd_mdot_k, pk_bd_mborder_k,
- * pk_bd_mxb_k, pk_bd_mscatter_k).  pk_band_solve_multi_dev solves K sol_c = rhs_c for k right-hand sides,
+/* MANY RIGHT-HAND SIDES AGAINST ONE FACTORISATION (the solve's six kernels pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k,
+ * pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k with a column count of k; DESIGN.md sections 27 and 28).
+ * pk_band_solve_multi_dev solves K sol_c = rhs_c for k right-hand sides,
  * 1 <= k <= 64, with the factors of the last pk_band_factor_dev, in the launches of ONE solve: right-hand side c is the n + m
  * doubles at d_rhs + c stride_rhs, its solution at d_sol + c stride_sol, both strides at least n + m.  The sweeps take one
  * workgroup per right-hand side; the border's columns of U are swept once per call and its Schur complement is formed and

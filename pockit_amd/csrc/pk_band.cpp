@@ -25,13 +25,13 @@
 //             in ascending order [pk_bd_update_k].  Every entry receives its updates in ascending pivot order whatever NB is,
 //             so the bits are those of the unblocked loop above.  A launch that finds status != 0 returns at once; the panel
 //             that fails writes nothing but the record.
-//   solve     R = p + 1 right-hand sides: the p columns of U, then b gathered through order[] (b_C aside) [pk_bd_prep_k]; one
-//             workgroup each [pk_bd_solve_k].  Forward, j ascending:
+//   solve     R = p + k sweep vectors (k = 1 for one right-hand side): the p columns of U, then each b gathered through order[]
+//             (its b_C aside) [pk_bd_prep_k]; one workgroup each [pk_bd_solve_k].  Forward, j ascending:
 //             y_j <-> y_ipiv[j], then y_i = y_i - (l_i y_j), i = j + 1 ... j + km.  Backward, k descending: y_k = y_k / B(k, k),
 //             then y_i = y_i - (B(i, k) y_k), i = max(0, k - 2 w) ... k - 1.  Elementwise: no sum is reduced across threads.
 //             The active window lives in an LDS ring, the factor's columns come in chunks of PK_BD_CH columns.
-//   border    (p > 0) the (p + 1) p dots d[r p + a] = U_a . Y_r by the pieced dot of pk_libkernel.h, products rounded before
-//             they are added [pk_bd_dot_k]; one workgroup: S(a, b) = C(a, b) - d[b p + a], t_a = b_C,a - d[p p + a], LU of S
+//   border    (p > 0) the (p + k) p dots d[r p + a] = U_a . Y_r by the pieced dot of pk_libkernel.h, products rounded before
+//             they are added [pk_bd_dot_k]; one workgroup: S(a, b) = C(a, b) - d[b p + a], t_a = b_C,a - d[(p + c) p + a], LU of S
 //             with partial pivoting (largest |.|, ties lowest) in plain loops, x_C by forward and back substitution, a pivot of
 //             0.0 gives status 2, one that is not finite status 3, column Nb + k [pk_bd_border_k]; then elementwise
 //             x_B,i = y_b,i - (Y_0,i x_C,0) - (Y_1,i x_C,1) ... in ascending q [pk_bd_xb_k].
@@ -41,11 +41,14 @@
 // permuted numbering or -1; 2 the smallest |pivot| of the band (+inf without one); 3 the largest (0.0 without one); 4 Nb; 5 w;
 // 6 p; 7 the interchanges that moved a row.  After status != 0 sol is left untouched.
 //
-//   block     k <= PK_BD_RHS_CAP right-hand sides against one factorisation in the launches of one solve: R = p + k sweep
-//             vectors (the p columns of U swept once per call), (p + k) p dots, S formed and factored ONCE by thread 0 of the
-//             border workgroup and thread c substituting for column c (the interchanges and multipliers are replayed on its own
-//             t in the order the single form applies them), x_B and the scatter over k (Nb + p) and k (n + m) elements
-//             [pk_bd_mprep_k ... pk_bd_mscatter_k].  Column c has the bits the single solve gives for it alone.
+//   forms     ONE family of ten kernels serves a single system, a batch and a block.  The grid is (work items, entries): a
+//             kernel takes its entry from blockIdx.y (bd_entry moves the pointers) and walks blockIdx.x; the single form is one
+//             entry with one column.  A batch is B <= PK_BD_BATCH_CAP systems behind one plan, each entry in its own slices.  A
+//             block is k <= PK_BD_RHS_CAP right-hand sides against one factorisation in the launches of one solve: the p columns
+//             of U are swept once per call, S is formed and factored ONCE by thread 0 of the border workgroup and thread c
+//             substitutes for column c (the interchanges and multipliers are replayed on its own t in the order the LU applied
+//             them to S), x_B and the scatter run over k Nb and k (n + m) elements.  Column c has the bits the solve gives for
+//             it alone, and entry e the bits of a batch of one.
 //
 // Pivoting is confined to the band part: a K whose band part B is singular while K is not fails here (status 1).
 // No atomics, no fused multiply-add, no workgroup waits for another: every dependency is a kernel boundary on the stream.
@@ -83,23 +86,20 @@ struct PkBandArgs {
   int32_t w, p, planes;
 };
 
-// A batch: B <= PK_BD_BATCH_CAP systems behind ONE plan (shape, map, order, where and j0 are shared).  `a` holds entry 0; entry
-// e's arrays begin e strides behind it, in elements of each array.  A stride of 0 (sources only) makes every entry read the same
-// array.  Y, x and b_C are slices of one work array per entry and move together.  No entry reads or writes another's slices.
-enum { PK_BD_BATCH_CAP = 16 };
-struct PkBandBatchArgs {
+// What every kernel takes: B <= PK_BD_BATCH_CAP entries behind ONE plan (shape, map, order, where and j0 are shared), each with
+// k <= PK_BD_RHS_CAP right-hand sides against its ONE factorisation.  The single form is B = 1, k = 1.
+//   entries   `a` holds entry 0; entry e's arrays begin e strides s_* behind it, in elements of each array.  A stride of 0
+//             (sources only) makes every entry read the same array.  Y, x and b_C are slices of one work array per entry and
+//             move together.  No entry reads or writes another's slices.
+//   columns   a.Y has p + k sweep vectors (U's columns, then the k right-hand sides), a.x k slices of nb + p, a.bc k slices of
+//             p, a.partial (p + k) p planes.  Column c reads a.rhs + c c_rhs and writes a.sol + c c_sol; the scatter reads
+//             slice c at a.x + c c_from.  At k = 1 these are the slices of one right-hand side.
+//   columns_j the trailing columns behind the panel at a.j0: the work items of the update launch.
+enum { PK_BD_BATCH_CAP = 16, PK_BD_RHS_CAP = 64 };
+struct PkBandFamilyArgs {
   PkBandArgs a;
   int64_t s_h, s_j, s_s1, s_s2, s_band, s_U, s_C, s_ipiv, s_work, s_rec, s_partial, s_rhs, s_sol;
-};
-
-// A block of right-hand sides: k <= PK_BD_RHS_CAP of them against ONE factorisation.  `a` holds the system; a.Y has p + k sweep
-// vectors (U's columns, then the k right-hand sides), a.x k slices of nb + p, a.bc k slices of p, a.partial (p + k) p planes.
-// Column c reads a.rhs + c s_rhs and writes a.sol + c s_sol; the scatter reads slice c at from + c s_from.
-enum { PK_BD_RHS_CAP = 64 };
-struct PkBandMultiArgs {
-  PkBandArgs a;
-  const double* from;
-  int64_t s_rhs, s_sol, s_from;
+  int64_t c_rhs, c_sol, c_from, columns_j;
   int32_t k;
 };
 static_assert(PK_BD_RHS_CAP <= PK_BLOCK, "one thread of the border workgroup per right-hand side");
@@ -115,6 +115,14 @@ static_assert(PK_BD_RHS_CAP <= PK_BLOCK, "one thread of the border workgroup per
     __syncthreads();                      \
   } while (0)
 #define BD_TREE(step, s, ...) lib_tree(step, s, (int)threadIdx.x, ##__VA_ARGS__)
+// The code behind this point begins on a 64-byte line of the instruction cache, whatever the length of the kernel's prologue
+// in front of it (the padding is s_nop, passed once).  The one-workgroup panel is a chain of ~200 barrier phases per panel, and
+// where its column loop falls against those lines is worth 2 us of its 74: measured, DESIGN.md section 28.
+#ifdef __HIP_DEVICE_COMPILE__
+#define BD_ALIGN_CODE() asm volatile(".p2align 6")
+#else
+#define BD_ALIGN_CODE() do {} while (0)
+#endif
 #else
 #define BD_BODY inline
 #define BD_PHASE(call)                                  \
@@ -122,6 +130,7 @@ static_assert(PK_BD_RHS_CAP <= PK_BLOCK, "one thread of the border workgroup per
     for (int t = 0; t < PK_BLOCK; ++t) { call; }        \
   } while (0)
 #define BD_TREE(step, s, ...) lib_tree_host(step, s, ##__VA_ARGS__)
+#define BD_ALIGN_CODE() do {} while (0)
 #endif
 
 PK_LIB_FN int64_t bd_min(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -133,9 +142,9 @@ PK_LIB_FN double* bd_at(const PkBandArgs& a, int64_t i, int64_t j) { return a.ba
 PK_LIB_FN bool bd_stored(const PkBandArgs& a, int64_t i, int64_t j) { return i - j <= a.w && j - i <= 2 * (int64_t)a.w; }
 PK_LIB_FN bool bd_fresh(const PkBandArgs& a, int64_t i, int64_t j) { return j - i > a.w && (a.j0 == 0 || j >= a.j0 + 2 * (int64_t)a.w); }
 
-// the arguments of entry e of a batch: every pointer moved by the entry's stride (an array the form does not use is null and
-// its stride 0), everything else as it is
-PK_LIB_FN PkBandArgs bd_entry(const PkBandBatchArgs& g, int64_t e) {
+// the arguments of entry e: every pointer moved by the entry's stride (an array the form does not use is null and its stride
+// 0), everything else as it is.  The only place that moves a pointer by an entry.
+PK_LIB_FN PkBandArgs bd_entry(const PkBandFamilyArgs& g, int64_t e) {
   PkBandArgs a = g.a;
   a.hvals += e * g.s_h; a.jvals += e * g.s_j; a.s1 += e * g.s_s1; a.s2 += e * g.s_s2;
   a.band += e * g.s_band; a.U += e * g.s_U; a.C += e * g.s_C;
@@ -170,28 +179,32 @@ PK_LIB_FN void bd_fill_element(const PkBandArgs& a, int64_t d) {
   a.band[d] = acc;      // (band, U and C are one array)
 }
 
-// [Y_0 ... Y_{p-1} | y_b | b_C] from U and the right-hand side
-PK_LIB_FN void bd_prep_element(const PkBandArgs& a, int64_t e) {
-  const int64_t nu = a.nb * a.p;
+// In the three elements below `a` is the entry's (bd_entry) and g gives the columns: k and the strides c_*.
+// [Y_0 ... Y_{p-1} | y_b of column 0 ... k - 1] and the k slices of b_C from U and the right-hand sides
+PK_LIB_FN void bd_prep_element(const PkBandArgs& a, const PkBandFamilyArgs& g, int64_t e) {
+  const int64_t nu = a.nb * a.p, N = a.nb + a.p;
   if (e < nu) { a.Y[e] = a.U[e]; return; }
-  const int64_t k = e - nu;      // the permuted position
-  const double v = a.rhs[a.order ? (int64_t)a.order[k] : k];
-  if (k < a.nb) a.Y[e] = v;
-  else a.bc[k - a.nb] = v;
+  const int64_t c = (e - nu) / N, k = (e - nu) % N;      // the column and the permuted position
+  const double v = a.rhs[c * g.c_rhs + (a.order ? (int64_t)a.order[k] : k)];
+  if (k < a.nb) a.Y[nu + c * a.nb + k] = v;
+  else a.bc[c * a.p + (k - a.nb)] = v;
 }
 
-PK_LIB_FN void bd_xb_element(const PkBandArgs& a, int64_t i) {
-  double v = a.Y[(int64_t)a.p * a.nb + i];
+PK_LIB_FN void bd_xb_element(const PkBandArgs& a, int64_t e) {
+  const int64_t c = e / a.nb, i = e % a.nb, N = a.nb + a.p;
+  double v = a.Y[((int64_t)a.p + c) * a.nb + i];
   for (int q = 0; q < a.p; ++q) {
-    const double pr = a.Y[(int64_t)q * a.nb + i] * a.x[a.nb + q];
+    const double pr = a.Y[(int64_t)q * a.nb + i] * a.x[c * N + a.nb + q];
     v = v - pr;
   }
-  a.x[i] = v;
+  a.x[c * N + i] = v;
 }
 
-PK_LIB_FN void bd_scatter_element(const PkBandArgs& a, int64_t i) {
+// (a.x is the scatter's source: x, or the swept right-hand sides without a border)
+PK_LIB_FN void bd_scatter_element(const PkBandArgs& a, const PkBandFamilyArgs& g, int64_t e) {
+  const int64_t c = e / a.nsol, i = e % a.nsol;
   const int64_t k = a.where ? (int64_t)a.where[i] : i;
-  a.sol[i] = k < 0 ? 0.0 : a.x[k];
+  a.sol[c * g.c_sol + i] = k < 0 ? 0.0 : a.x[c * g.c_from + k];
 }
 
 // ---------------------------------------------------------------- the panel: threads of the one workgroup
@@ -257,6 +270,7 @@ BD_BODY void bd_panel_body(const PkBandArgs& a, double* T, double* s, int* piv) 
   const int nbp = (int)bd_min(PK_BD_NB, a.nb - a.j0), rows = (int)bd_min((int64_t)a.w + nbp, a.nb - a.j0);
   double pmin = a.rec[BD_MIN], pmax = a.rec[BD_MAX], swaps = a.rec[BD_SWAPS];
   BD_PHASE(bd_panel_load(a, T, t, nbp, rows));
+  BD_ALIGN_CODE();
   for (int jj = 0; jj < nbp; ++jj) {
     const int km = (int)bd_min(a.w, a.nb - 1 - (a.j0 + jj));
     BD_PHASE(bd_amax_load(T, s, t, jj, km));
@@ -422,93 +436,10 @@ PK_LIB_FN void bd_dot_store(const PkBandArgs& a, int64_t r, int64_t pc, int q, c
 PK_LIB_FN void bd_dots_keep(double* dots, const double* s, int t, int r, int p) {
   if (t < p) dots[r * p + t] = s[t * PK_BLOCK];
 }
-// thread 0: S = C - U^T Y_U, t = b_C - U^T y_b, LU with partial pivoting, x_C
-PK_LIB_FN void bd_border_thread(const PkBandArgs& a, int t, const double* dots, double* S, double* v) {
-  if (t != 0) return;
-  const int p = a.p;
-  for (int c = 0; c < p; ++c)
-    for (int r = 0; r < p; ++r) S[r + c * p] = a.C[r + c * p] - dots[c * p + r];
-  for (int r = 0; r < p; ++r) v[r] = a.bc[r] - dots[p * p + r];
-  for (int k = 0; k < p; ++k) {
-    int ip = k;
-    double big = -1.0;
-    for (int r = k; r < p; ++r) {
-      const double e = S[r + k * p];
-      const double m = __builtin_isfinite(e) ? __builtin_fabs(e) : __builtin_inf();
-      if (m > big) { big = m; ip = r; }
-    }
-    if (!__builtin_isfinite(big) || big == 0.0) {
-      a.rec[BD_STATUS] = __builtin_isfinite(big) ? 2.0 : 3.0;
-      a.rec[BD_COLUMN] = (double)(a.nb + k);
-      return;
-    }
-    if (ip != k) {
-      for (int c = 0; c < p; ++c) { const double u = S[k + c * p]; S[k + c * p] = S[ip + c * p]; S[ip + c * p] = u; }
-      const double u = v[k]; v[k] = v[ip]; v[ip] = u;
-    }
-    for (int r = k + 1; r < p; ++r) {
-      const double l = S[r + k * p] / S[k + k * p];
-      S[r + k * p] = l;
-      for (int c = k + 1; c < p; ++c) { const double pr = l * S[k + c * p]; S[r + c * p] = S[r + c * p] - pr; }
-      const double pr = l * v[k];
-      v[r] = v[r] - pr;
-    }
-  }
-  for (int k = p - 1; k >= 0; --k) {
-    double e = v[k];
-    for (int c = k + 1; c < p; ++c) { const double pr = S[k + c * p] * v[c]; e = e - pr; }
-    v[k] = e / S[k + k * p];
-  }
-  for (int k = 0; k < p; ++k) a.x[a.nb + k] = v[k];
-}
-
-BD_BODY void bd_border_body(const PkBandArgs& a, double* s, double* dots, double* S, double* v) {
-  if (a.rec[BD_STATUS] != 0.0) return;
-  for (int r = 0; r <= a.p; ++r) {
-    PkBandArgs b = a;
-    b.partial = a.partial + (int64_t)r * a.p * a.n_pieces;
-    b.planes = a.p;
-    BD_PHASE(lib_scalar_thread(b, t, s));
-    BD_TREE(lib_planes_step, s, (int)a.p);
-    BD_PHASE(bd_dots_keep(dots, s, t, r, a.p));
-  }
-  BD_PHASE(bd_border_thread(a, t, dots, S, v));
-}
-
-// ---------------------------------------------------------------- the block of k right-hand sides
-// [Y_0 ... Y_{p-1} | y_b of column 0 ... k - 1] and the k slices of b_C from U and the right-hand sides
-PK_LIB_FN void bd_mprep_element(const PkBandMultiArgs& g, int64_t e) {
-  const PkBandArgs& a = g.a;
-  const int64_t nu = a.nb * a.p, N = a.nb + a.p;
-  if (e < nu) { a.Y[e] = a.U[e]; return; }
-  const int64_t c = (e - nu) / N, k = (e - nu) % N;      // the column and the permuted position
-  const double v = a.rhs[c * g.s_rhs + (a.order ? (int64_t)a.order[k] : k)];
-  if (k < a.nb) a.Y[nu + c * a.nb + k] = v;
-  else a.bc[c * a.p + (k - a.nb)] = v;
-}
-
-PK_LIB_FN void bd_mxb_element(const PkBandMultiArgs& g, int64_t e) {
-  const PkBandArgs& a = g.a;
-  const int64_t c = e / a.nb, i = e % a.nb, N = a.nb + a.p;
-  double v = a.Y[((int64_t)a.p + c) * a.nb + i];
-  for (int q = 0; q < a.p; ++q) {
-    const double pr = a.Y[(int64_t)q * a.nb + i] * a.x[c * N + a.nb + q];
-    v = v - pr;
-  }
-  a.x[c * N + i] = v;
-}
-
-PK_LIB_FN void bd_mscatter_element(const PkBandMultiArgs& g, int64_t e) {
-  const PkBandArgs& a = g.a;
-  const int64_t c = e / a.nsol, i = e % a.nsol;
-  const int64_t k = a.where ? (int64_t)a.where[i] : i;
-  a.sol[c * g.s_sol + i] = k < 0 ? 0.0 : g.from[c * g.s_from + k];
-}
-
-// thread 0: S = C - U^T Y_U and its LU with partial pivoting, ONCE for the block.  The multipliers are kept as they are formed
-// (L[r + k p], never exchanged afterwards) beside the interchanges piv[k], so that a column can replay on its own t exactly
-// what bd_border_thread does to v; piv[p] is 1 after a failed pivot.
-PK_LIB_FN void bd_mborder_factor(const PkBandArgs& a, int t, const double* dots, double* S, double* L, int* piv) {
+// thread 0: S = C - U^T Y_U and its LU with partial pivoting, ONCE for the k columns.  The multipliers are kept as they are
+// formed (L[r + k p], never exchanged afterwards) beside the interchanges piv[k], so that a column can replay on its own t
+// exactly what an LU of [S | t] would do to t, step by step; piv[p] is 1 after a failed pivot.
+PK_LIB_FN void bd_border_factor(const PkBandArgs& a, int t, const double* dots, double* S, double* L, int* piv) {
   if (t != 0) return;
   const int p = a.p;
   piv[p] = 0;
@@ -541,11 +472,10 @@ PK_LIB_FN void bd_mborder_factor(const PkBandArgs& a, int t, const double* dots,
 }
 // thread c < k: t = b_C - U^T y_b of column c, the interchanges and multipliers replayed, the back substitution; v is the
 // column's own slice of P_CAP doubles
-PK_LIB_FN void bd_mborder_column(const PkBandMultiArgs& g, int c, const double* dots, const double* S, const double* L, const int* piv,
-                                 double* vs) {
-  const PkBandArgs& a = g.a;
+PK_LIB_FN void bd_border_column(const PkBandArgs& a, int k_rhs, int c, const double* dots, const double* S, const double* L, const int* piv,
+                                double* vs) {
   const int p = a.p;
-  if (c >= g.k || piv[p] != 0) return;
+  if (c >= k_rhs || piv[p] != 0) return;
   double* v = vs + c * PK_BD_P_CAP;
   for (int r = 0; r < p; ++r) v[r] = a.bc[(int64_t)c * p + r] - dots[(p + c) * p + r];
   for (int k = 0; k < p; ++k) {
@@ -564,10 +494,9 @@ PK_LIB_FN void bd_mborder_column(const PkBandMultiArgs& g, int c, const double* 
   for (int k = 0; k < p; ++k) a.x[(int64_t)c * (a.nb + p) + a.nb + k] = v[k];
 }
 
-BD_BODY void bd_mborder_body(const PkBandMultiArgs& g, double* s, double* dots, double* S, double* L, int* piv, double* vs) {
-  const PkBandArgs& a = g.a;
+BD_BODY void bd_border_body(const PkBandArgs& a, int k_rhs, double* s, double* dots, double* S, double* L, int* piv, double* vs) {
   if (a.rec[BD_STATUS] != 0.0) return;
-  for (int r = 0; r < a.p + g.k; ++r) {
+  for (int r = 0; r < a.p + k_rhs; ++r) {
     PkBandArgs b = a;
     b.partial = a.partial + (int64_t)r * a.p * a.n_pieces;
     b.planes = a.p;
@@ -575,103 +504,19 @@ BD_BODY void bd_mborder_body(const PkBandMultiArgs& g, double* s, double* dots, 
     BD_TREE(lib_planes_step, s, (int)a.p);
     BD_PHASE(bd_dots_keep(dots, s, t, r, a.p));
   }
-  BD_PHASE(bd_mborder_factor(a, t, dots, S, L, piv));
-  BD_PHASE(bd_mborder_column(g, t, dots, S, L, piv, vs));
+  BD_PHASE(bd_border_factor(a, t, dots, S, L, piv));
+  BD_PHASE(bd_border_column(a, k_rhs, t, dots, S, L, piv, vs));
 }
 
 #ifdef __HIPCC__
-// ---------------------------------------------------------------- kernels (gfx950)
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_init_k(PkBandArgs a) { bd_init_thread(a, (int)threadIdx.x); }
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_fill_k(PkBandArgs a) {
-  const int64_t items = bd_items(a.dests);
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t d = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (d < a.dests) bd_fill_element(a, d);
-  }
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_panel_k(PkBandArgs a) {
-  __shared__ double T[BD_LD * PK_BD_NB];
-  __shared__ double s[2 * PK_BLOCK];
-  __shared__ int piv[PK_BD_NB];
-  bd_panel_body(a, T, s, piv);
-}
-
-// work item = a trailing column
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_update_k(PkBandArgs a, int64_t columns) {
-  __shared__ double col[PK_BLOCK];
-  for (int64_t item = (int64_t)blockIdx.x; item < columns; item += (int64_t)gridDim.x) bd_update_body(a, item, col);
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_prep_k(PkBandArgs a) {
-  const int64_t len = a.nb * (a.p + 1) + a.p, items = bd_items(len);
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (e < len) bd_prep_element(a, e);
-  }
-}
-
-// work item = a right-hand side
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_solve_k(PkBandArgs a) {
-  __shared__ double F[PK_BD_CH * BD_LW];
-  __shared__ double ring[PK_BD_RING];
-  __shared__ int ipl[PK_BD_CH];
-  for (int64_t q = (int64_t)blockIdx.x; q <= a.p; q += (int64_t)gridDim.x) bd_solve_body(a, q, F, ring, ipl);
-}
-
-// work item = right-hand side * n_pieces + piece
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_dot_k(PkBandArgs a) {
-  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
-  const int t = (int)threadIdx.x;
-  const int64_t items = (a.p + 1) * a.n_pieces;
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t r = item / a.n_pieces, pc = item % a.n_pieces;
-    bd_dot_thread(a, r, pc, t, s);
-    __syncthreads();
-    lib_tree(lib_planes_step, s, t, (int)a.p);
-    if (t < a.p) bd_dot_store(a, r, pc, t, s);
-    __syncthreads();
-  }
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_border_k(PkBandArgs a) {
-  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
-  __shared__ double dots[(PK_BD_P_CAP + 1) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], v[PK_BD_P_CAP];
-  bd_border_body(a, s, dots, S, v);
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_xb_k(PkBandArgs a) {
-  if (a.rec[BD_STATUS] != 0.0) return;
-  const int64_t items = bd_items(a.nb);
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t i = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (i < a.nb) bd_xb_element(a, i);
-  }
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_scatter_k(PkBandArgs a) {
-  if (a.rec[BD_STATUS] != 0.0) return;
-  const int64_t items = bd_items(a.nsol);
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t i = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (i < a.nsol) bd_scatter_element(a, i);
-  }
-}
-#define BD_LAUNCH_UPDATE(c, grid, st, a, columns)                                                   \
-  do {                                                                                              \
-    hipLaunchKernelGGL(pk_bd_update_k, dim3(grid), dim3(PK_BLOCK), 0, (st), (a), (columns));        \
-    PK_HIP((c), hipGetLastError());                                                                 \
-  } while (0)
-
-// ---------------------------------------------------------------- the batch kernels: grid (the single kernel's, B)
-// Entry blockIdx.y's arguments, then the single kernel's walk of blockIdx.x over the same body with the same static LDS.
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_init_bk(PkBandBatchArgs g) {
+// ---------------------------------------------------------------- kernels (gfx950): grid (work items, entries)
+// Entry blockIdx.y's arguments, then the walk of blockIdx.x over the body.
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_init_k(PkBandFamilyArgs g) {
   const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
   bd_init_thread(a, (int)threadIdx.x);
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_fill_bk(PkBandBatchArgs g) {
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_fill_k(PkBandFamilyArgs g) {
   const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
   const int64_t items = bd_items(a.dests);
   for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
@@ -680,7 +525,7 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_bd_fill_bk(PkBandBatchArgs g) {
   }
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_panel_bk(PkBandBatchArgs g) {
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_panel_k(PkBandFamilyArgs g) {
   __shared__ double T[BD_LD * PK_BD_NB];
   __shared__ double s[2 * PK_BLOCK];
   __shared__ int piv[PK_BD_NB];
@@ -688,97 +533,36 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_bd_panel_bk(PkBandBatchArgs g) {
   bd_panel_body(a, T, s, piv);
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_update_bk(PkBandBatchArgs g, int64_t columns) {
+// work item = a trailing column
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_update_k(PkBandFamilyArgs g) {
   __shared__ double col[PK_BLOCK];
   const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
-  for (int64_t item = (int64_t)blockIdx.x; item < columns; item += (int64_t)gridDim.x) bd_update_body(a, item, col);
+  for (int64_t item = (int64_t)blockIdx.x; item < g.columns_j; item += (int64_t)gridDim.x) bd_update_body(a, item, col);
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_prep_bk(PkBandBatchArgs g) {
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_prep_k(PkBandFamilyArgs g) {
   const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
-  const int64_t len = a.nb * (a.p + 1) + a.p, items = bd_items(len);
+  const int64_t len = a.nb * a.p + (int64_t)g.k * (a.nb + a.p), items = bd_items(len);
   for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
     const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (e < len) bd_prep_element(a, e);
-  }
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_solve_bk(PkBandBatchArgs g) {
-  __shared__ double F[PK_BD_CH * BD_LW];
-  __shared__ double ring[PK_BD_RING];
-  __shared__ int ipl[PK_BD_CH];
-  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
-  for (int64_t q = (int64_t)blockIdx.x; q <= a.p; q += (int64_t)gridDim.x) bd_solve_body(a, q, F, ring, ipl);
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_dot_bk(PkBandBatchArgs g) {
-  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
-  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
-  const int t = (int)threadIdx.x;
-  const int64_t items = (a.p + 1) * a.n_pieces;
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t r = item / a.n_pieces, pc = item % a.n_pieces;
-    bd_dot_thread(a, r, pc, t, s);
-    __syncthreads();
-    lib_tree(lib_planes_step, s, t, (int)a.p);
-    if (t < a.p) bd_dot_store(a, r, pc, t, s);
-    __syncthreads();
-  }
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_border_bk(PkBandBatchArgs g) {
-  __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
-  __shared__ double dots[(PK_BD_P_CAP + 1) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], v[PK_BD_P_CAP];
-  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
-  bd_border_body(a, s, dots, S, v);
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_xb_bk(PkBandBatchArgs g) {
-  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
-  if (a.rec[BD_STATUS] != 0.0) return;
-  const int64_t items = bd_items(a.nb);
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t i = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (i < a.nb) bd_xb_element(a, i);
-  }
-}
-
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_scatter_bk(PkBandBatchArgs g) {
-  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
-  if (a.rec[BD_STATUS] != 0.0) return;
-  const int64_t items = bd_items(a.nsol);
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t i = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (i < a.nsol) bd_scatter_element(a, i);
-  }
-}
-#define BD_LAUNCH_UPDATE_Y(c, grid, ny, st, g, columns)                                                      \
-  do {                                                                                                       \
-    hipLaunchKernelGGL(pk_bd_update_bk, dim3((grid), (ny)), dim3(PK_BLOCK), 0, (st), (g), (columns));        \
-    PK_HIP((c), hipGetLastError());                                                                          \
-  } while (0)
-
-// ---------------------------------------------------------------- the block kernels: k right-hand sides, one factorisation
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mprep_k(PkBandMultiArgs g) {
-  const int64_t len = g.a.nb * g.a.p + (int64_t)g.k * (g.a.nb + g.a.p), items = bd_items(len);
-  for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
-    const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (e < len) bd_mprep_element(g, e);
+    if (e < len) bd_prep_element(a, g, e);
   }
 }
 
 // work item = a sweep vector: a column of U or a right-hand side
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_msolve_k(PkBandMultiArgs g) {
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_solve_k(PkBandFamilyArgs g) {
   __shared__ double F[PK_BD_CH * BD_LW];
   __shared__ double ring[PK_BD_RING];
   __shared__ int ipl[PK_BD_CH];
-  const int64_t R = (int64_t)g.a.p + g.k;
-  for (int64_t q = (int64_t)blockIdx.x; q < R; q += (int64_t)gridDim.x) bd_solve_body(g.a, q, F, ring, ipl);
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  const int64_t R = (int64_t)a.p + g.k;
+  for (int64_t q = (int64_t)blockIdx.x; q < R; q += (int64_t)gridDim.x) bd_solve_body(a, q, F, ring, ipl);
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mdot_k(PkBandMultiArgs g) {
+// work item = sweep vector * n_pieces + piece
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_dot_k(PkBandFamilyArgs g) {
   __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
-  const PkBandArgs& a = g.a;
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
   const int t = (int)threadIdx.x;
   const int64_t items = ((int64_t)a.p + g.k) * a.n_pieces;
   for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
@@ -791,104 +575,67 @@ __global__ void __launch_bounds__(PK_BLOCK) pk_bd_mdot_k(PkBandMultiArgs g) {
   }
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mborder_k(PkBandMultiArgs g) {
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_border_k(PkBandFamilyArgs g) {
   __shared__ double s[PK_BD_P_CAP * PK_BLOCK];
   __shared__ double dots[(PK_BD_P_CAP + PK_BD_RHS_CAP) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], L[PK_BD_P_CAP * PK_BD_P_CAP];
   __shared__ double vs[PK_BD_RHS_CAP * PK_BD_P_CAP];
   __shared__ int piv[PK_BD_P_CAP + 1];
-  bd_mborder_body(g, s, dots, S, L, piv, vs);
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  bd_border_body(a, (int)g.k, s, dots, S, L, piv, vs);
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mxb_k(PkBandMultiArgs g) {
-  if (g.a.rec[BD_STATUS] != 0.0) return;
-  const int64_t len = (int64_t)g.k * g.a.nb, items = bd_items(len);
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_xb_k(PkBandFamilyArgs g) {
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  if (a.rec[BD_STATUS] != 0.0) return;
+  const int64_t len = (int64_t)g.k * a.nb, items = bd_items(len);
   for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
     const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (e < len) bd_mxb_element(g, e);
+    if (e < len) bd_xb_element(a, e);
   }
 }
 
-__global__ void __launch_bounds__(PK_BLOCK) pk_bd_mscatter_k(PkBandMultiArgs g) {
-  if (g.a.rec[BD_STATUS] != 0.0) return;
-  const int64_t len = (int64_t)g.k * g.a.nsol, items = bd_items(len);
+__global__ void __launch_bounds__(PK_BLOCK) pk_bd_scatter_k(PkBandFamilyArgs g) {
+  const PkBandArgs a = bd_entry(g, (int64_t)blockIdx.y);
+  if (a.rec[BD_STATUS] != 0.0) return;
+  const int64_t len = (int64_t)g.k * a.nsol, items = bd_items(len);
   for (int64_t item = (int64_t)blockIdx.x; item < items; item += (int64_t)gridDim.x) {
     const int64_t e = item * PK_BLOCK + (int64_t)threadIdx.x;
-    if (e < len) bd_mscatter_element(g, e);
+    if (e < len) bd_scatter_element(a, g, e);
   }
 }
 #else
-// ---------------------------------------------------------------- host stand-in: the identical walk
-static void bd_init_host(const PkBandArgs& a, unsigned) { bd_init_thread(a, 0); }
-static void bd_fill_host(const PkBandArgs& a, unsigned grid) {
+// ---------------------------------------------------------------- host stand-in: the identical walk of entry y
+// (PK_LIB_LAUNCH_Y walks the entries outermost)
+static void bd_init_host(const PkBandFamilyArgs& g, unsigned, unsigned y) { bd_init_thread(bd_entry(g, y), 0); }
+static void bd_fill_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y) {
+  const PkBandArgs a = bd_entry(g, y);
   lib_elements_host(grid, a.dests, [&](int64_t d) { bd_fill_element(a, d); });
 }
-static void bd_panel_host(const PkBandArgs& a, unsigned) {
+static void bd_panel_host(const PkBandFamilyArgs& g, unsigned, unsigned y) {
   static double T[BD_LD * PK_BD_NB];
   double s[2 * PK_BLOCK];
   int piv[PK_BD_NB];
-  bd_panel_body(a, T, s, piv);
+  bd_panel_body(bd_entry(g, y), T, s, piv);
 }
-static void bd_update_host(const PkBandArgs& a, unsigned grid, int64_t columns) {
+static void bd_update_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y) {
+  const PkBandArgs a = bd_entry(g, y);
   double col[PK_BLOCK];
-  lib_walk_host(grid, columns, [&](int64_t item) { bd_update_body(a, item, col); });
+  lib_walk_host(grid, g.columns_j, [&](int64_t item) { bd_update_body(a, item, col); });
 }
-static void bd_prep_host(const PkBandArgs& a, unsigned grid) {
-  lib_elements_host(grid, a.nb * (a.p + 1) + a.p, [&](int64_t e) { bd_prep_element(a, e); });
+static void bd_prep_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y) {
+  const PkBandArgs a = bd_entry(g, y);
+  lib_elements_host(grid, a.nb * a.p + (int64_t)g.k * (a.nb + a.p), [&](int64_t e) { bd_prep_element(a, g, e); });
 }
-static void bd_solve_host(const PkBandArgs& a, unsigned grid) {
+static void bd_solve_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y) {
   static double F[PK_BD_CH * BD_LW];
   double ring[PK_BD_RING];
   int ipl[PK_BD_CH];
-  lib_walk_host(grid, (int64_t)a.p + 1, [&](int64_t q) { bd_solve_body(a, q, F, ring, ipl); });
+  const PkBandArgs a = bd_entry(g, y);
+  lib_walk_host(grid, (int64_t)a.p + g.k, [&](int64_t q) { bd_solve_body(a, q, F, ring, ipl); });
 }
-static void bd_dot_host(const PkBandArgs& a, unsigned grid) {
+static void bd_dot_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y) {
   static double s[PK_BD_P_CAP * PK_BLOCK];
-  lib_walk_host(grid, (a.p + 1) * a.n_pieces, [&](int64_t item) {
-    const int64_t r = item / a.n_pieces, pc = item % a.n_pieces;
-    for (int t = 0; t < PK_BLOCK; ++t) bd_dot_thread(a, r, pc, t, s);
-    lib_tree_host(lib_planes_step, s, (int)a.p);
-    for (int q = 0; q < a.p; ++q) bd_dot_store(a, r, pc, q, s);
-  });
-}
-static void bd_border_host(const PkBandArgs& a, unsigned) {
-  static double s[PK_BD_P_CAP * PK_BLOCK];
-  double dots[(PK_BD_P_CAP + 1) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], v[PK_BD_P_CAP];
-  bd_border_body(a, s, dots, S, v);
-}
-static void bd_xb_host(const PkBandArgs& a, unsigned grid) {
-  if (a.rec[BD_STATUS] != 0.0) return;
-  lib_elements_host(grid, a.nb, [&](int64_t i) { bd_xb_element(a, i); });
-}
-static void bd_scatter_host(const PkBandArgs& a, unsigned grid) {
-  if (a.rec[BD_STATUS] != 0.0) return;
-  lib_elements_host(grid, a.nsol, [&](int64_t i) { bd_scatter_element(a, i); });
-}
-#define BD_LAUNCH_UPDATE(c, grid, st, a, columns) \
-  fake_hip_enqueue((st), [a_ = (a), g_ = (grid), n_ = (columns)]() { bd_update_host(a_, g_, n_); })
-
-// the batch kernels' stand-ins: entry y's arguments, then the single form's walk (PK_LIB_LAUNCH_Y walks the entries outermost)
-static void bd_init_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_init_host(bd_entry(g, y), grid); }
-static void bd_fill_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_fill_host(bd_entry(g, y), grid); }
-static void bd_panel_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_panel_host(bd_entry(g, y), grid); }
-static void bd_prep_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_prep_host(bd_entry(g, y), grid); }
-static void bd_solve_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_solve_host(bd_entry(g, y), grid); }
-static void bd_dot_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_dot_host(bd_entry(g, y), grid); }
-static void bd_border_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_border_host(bd_entry(g, y), grid); }
-static void bd_xb_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_xb_host(bd_entry(g, y), grid); }
-static void bd_scatter_bhost(const PkBandBatchArgs& g, unsigned grid, unsigned y) { bd_scatter_host(bd_entry(g, y), grid); }
-// the block kernels' stand-ins
-static void bd_mprep_host(const PkBandMultiArgs& g, unsigned grid) {
-  lib_elements_host(grid, g.a.nb * g.a.p + (int64_t)g.k * (g.a.nb + g.a.p), [&](int64_t e) { bd_mprep_element(g, e); });
-}
-static void bd_msolve_host(const PkBandMultiArgs& g, unsigned grid) {
-  static double F[PK_BD_CH * BD_LW];
-  double ring[PK_BD_RING];
-  int ipl[PK_BD_CH];
-  lib_walk_host(grid, (int64_t)g.a.p + g.k, [&](int64_t q) { bd_solve_body(g.a, q, F, ring, ipl); });
-}
-static void bd_mdot_host(const PkBandMultiArgs& g, unsigned grid) {
-  static double s[PK_BD_P_CAP * PK_BLOCK];
-  const PkBandArgs& a = g.a;
+  const PkBandArgs a = bd_entry(g, y);
   lib_walk_host(grid, ((int64_t)a.p + g.k) * a.n_pieces, [&](int64_t item) {
     const int64_t r = item / a.n_pieces, pc = item % a.n_pieces;
     for (int t = 0; t < PK_BLOCK; ++t) bd_dot_thread(a, r, pc, t, s);
@@ -896,25 +643,23 @@ static void bd_mdot_host(const PkBandMultiArgs& g, unsigned grid) {
     for (int q = 0; q < a.p; ++q) bd_dot_store(a, r, pc, q, s);
   });
 }
-static void bd_mborder_host(const PkBandMultiArgs& g, unsigned) {
+static void bd_border_host(const PkBandFamilyArgs& g, unsigned, unsigned y) {
   static double s[PK_BD_P_CAP * PK_BLOCK];
   double dots[(PK_BD_P_CAP + PK_BD_RHS_CAP) * PK_BD_P_CAP], S[PK_BD_P_CAP * PK_BD_P_CAP], L[PK_BD_P_CAP * PK_BD_P_CAP];
   double vs[PK_BD_RHS_CAP * PK_BD_P_CAP];
   int piv[PK_BD_P_CAP + 1];
-  bd_mborder_body(g, s, dots, S, L, piv, vs);
+  bd_border_body(bd_entry(g, y), (int)g.k, s, dots, S, L, piv, vs);
 }
-static void bd_mxb_host(const PkBandMultiArgs& g, unsigned grid) {
-  if (g.a.rec[BD_STATUS] != 0.0) return;
-  lib_elements_host(grid, (int64_t)g.k * g.a.nb, [&](int64_t e) { bd_mxb_element(g, e); });
+static void bd_xb_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y) {
+  const PkBandArgs a = bd_entry(g, y);
+  if (a.rec[BD_STATUS] != 0.0) return;
+  lib_elements_host(grid, (int64_t)g.k * a.nb, [&](int64_t e) { bd_xb_element(a, e); });
 }
-static void bd_mscatter_host(const PkBandMultiArgs& g, unsigned grid) {
-  if (g.a.rec[BD_STATUS] != 0.0) return;
-  lib_elements_host(grid, (int64_t)g.k * g.a.nsol, [&](int64_t e) { bd_mscatter_element(g, e); });
+static void bd_scatter_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y) {
+  const PkBandArgs a = bd_entry(g, y);
+  if (a.rec[BD_STATUS] != 0.0) return;
+  lib_elements_host(grid, (int64_t)g.k * a.nsol, [&](int64_t e) { bd_scatter_element(a, g, e); });
 }
-#define BD_LAUNCH_UPDATE_Y(c, grid, ny, st, g, columns)                                                \
-  fake_hip_enqueue((st), [a_ = (g), g_ = (grid), y_ = (unsigned)(ny), n_ = (columns)]() {              \
-    for (unsigned y = 0; y < y_; ++y) bd_update_host(bd_entry(a_, y), g_, n_);                         \
-  })
 #endif
 
 void free_band(pk_ctx* c) {
@@ -940,40 +685,46 @@ int bd_shape(pk_ctx* c, int64_t nb, int64_t w, int64_t p, const char* who) {
   return 0;
 }
 
-// the rest of a solve's work behind the matrix, into the arguments
-void bd_solve_slices(PkBandArgs& a, double* work) {
+// the slices of a solve's work for k right-hand sides, into the arguments: [Y | x | b_C]
+void bd_solve_slices(PkBandArgs& a, int64_t k, double* work) {
   a.Y = work;
-  a.x = a.Y + a.nb * (a.p + 1);
-  a.bc = a.x + (a.nb + a.p);
+  a.x = a.Y + a.nb * (a.p + k);
+  a.bc = a.x + k * (a.nb + a.p);
 }
 
-// init, the panels and the updates behind them: the arguments hold band, ipiv, rec and the shape
-int bd_enqueue_factor(pk_ctx* c, PkBandArgs a, bool fill, hipStream_t st) {
-  PK_LIB_LAUNCH(c, pk_bd_init_k, bd_init_host, 1u, st, a);
-  if (fill && a.dests > 0) PK_LIB_LAUNCH(c, pk_bd_fill_k, bd_fill_host, lib_grid(lib_elem_items(a.dests)), st, a);
+// init, the panels and the updates behind them for B entries: the arguments hold band, ipiv, rec and the shape
+int bd_enqueue_factor(pk_ctx* c, PkBandFamilyArgs g, int32_t B, bool fill, hipStream_t st) {
+  const PkBandArgs& a = g.a;
+  PK_LIB_LAUNCH_Y(c, pk_bd_init_k, bd_init_host, 1u, B, st, g);
+  if (fill && a.dests > 0) PK_LIB_LAUNCH_Y(c, pk_bd_fill_k, bd_fill_host, lib_grid(lib_elem_items(a.dests)), B, st, g);
   for (int64_t j0 = 0; j0 < a.nb; j0 += PK_BD_NB) {
-    a.j0 = j0;
-    PK_LIB_LAUNCH(c, pk_bd_panel_k, bd_panel_host, 1u, st, a);
+    g.a.j0 = j0;
+    PK_LIB_LAUNCH_Y(c, pk_bd_panel_k, bd_panel_host, 1u, B, st, g);
     const int64_t j1 = std::min<int64_t>(j0 + PK_BD_NB, a.nb);
-    const int64_t columns = std::min<int64_t>(j1 - 1 + 2 * (int64_t)a.w, a.nb - 1) - j1 + 1;
-    if (columns > 0) BD_LAUNCH_UPDATE(c, lib_grid(columns), st, a, columns);
+    g.columns_j = std::min<int64_t>(j1 - 1 + 2 * (int64_t)a.w, a.nb - 1) - j1 + 1;
+    if (g.columns_j > 0) PK_LIB_LAUNCH_Y(c, pk_bd_update_k, bd_update_host, lib_grid(g.columns_j), B, st, g);
   }
   return 0;
 }
 
-// right-hand sides, sweeps, border and scatter: the arguments hold everything
-int bd_enqueue_solve(pk_ctx* c, PkBandArgs a, hipStream_t st) {
-  if (a.nb + a.p > 0) PK_LIB_LAUNCH(c, pk_bd_prep_k, bd_prep_host, lib_grid(lib_elem_items(a.nb * (a.p + 1) + a.p)), st, a);
-  if (a.nb > 0) PK_LIB_LAUNCH(c, pk_bd_solve_k, bd_solve_host, lib_grid((int64_t)a.p + 1), st, a);
-  double* from = a.Y;      // (without a border the solution is y_b itself)
+// right-hand sides, sweeps, border and scatter for B entries of k columns, in the launches of ONE solve (3 without a border, 6
+// with one): the arguments hold everything but the scatter's source
+int bd_enqueue_solve(pk_ctx* c, PkBandFamilyArgs g, int32_t B, hipStream_t st) {
+  const PkBandArgs& a = g.a;
+  const int64_t k = g.k, N = a.nb + a.p;
+  if (N > 0) PK_LIB_LAUNCH_Y(c, pk_bd_prep_k, bd_prep_host, lib_grid(lib_elem_items(a.nb * a.p + k * N)), B, st, g);
+  if (a.nb > 0) PK_LIB_LAUNCH_Y(c, pk_bd_solve_k, bd_solve_host, lib_grid((int64_t)a.p + k), B, st, g);
+  double* from = a.Y;      // (without a border the solutions are the swept right-hand sides themselves; Y and x move by the same stride)
+  g.c_from = a.nb;
   if (a.p > 0) {
-    PK_LIB_LAUNCH(c, pk_bd_dot_k, bd_dot_host, lib_grid((a.p + 1) * a.n_pieces), st, a);
-    PK_LIB_LAUNCH(c, pk_bd_border_k, bd_border_host, 1u, st, a);
-    if (a.nb > 0) PK_LIB_LAUNCH(c, pk_bd_xb_k, bd_xb_host, lib_grid(lib_elem_items(a.nb)), st, a);
+    PK_LIB_LAUNCH_Y(c, pk_bd_dot_k, bd_dot_host, lib_grid(((int64_t)a.p + k) * a.n_pieces), B, st, g);
+    PK_LIB_LAUNCH_Y(c, pk_bd_border_k, bd_border_host, 1u, B, st, g);
+    if (a.nb > 0) PK_LIB_LAUNCH_Y(c, pk_bd_xb_k, bd_xb_host, lib_grid(lib_elem_items(k * a.nb)), B, st, g);
     from = a.x;
+    g.c_from = N;
   }
-  a.x = from;
-  if (a.nsol > 0) PK_LIB_LAUNCH(c, pk_bd_scatter_k, bd_scatter_host, lib_grid(lib_elem_items(a.nsol)), st, a);
+  g.a.x = from;
+  if (a.nsol > 0) PK_LIB_LAUNCH_Y(c, pk_bd_scatter_k, bd_scatter_host, lib_grid(lib_elem_items(k * a.nsol)), B, st, g);
   return 0;
 }
 
@@ -993,53 +744,46 @@ int bd_context(pk_ctx* c, const char* who) {
   return 0;
 }
 
-// the arguments of the planned system: the matrix, ipiv and the record in the context's arrays
-PkBandArgs bd_planned(pk_ctx* c) {
+// is there a plan, and do the CSR maps still have the sources it was made for?
+int bd_plan_current(pk_ctx* c, const char* who) {
+  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
+  if (c->band.sources != c->csr[1].n_unique + c->csr[0].n_unique + (int64_t)c->n + c->m)
+    return fail(c, 134, "%s: the CSR maps changed since pk_band_plan", who);
+  return 0;
+}
+
+// the arguments of the planned system, one entry with one column: the matrix, ipiv and the record in the context's arrays
+PkBandFamilyArgs bd_planned(pk_ctx* c) {
   const PkBand& b = c->band;
-  PkBandArgs a{};
+  PkBandFamilyArgs g{};
+  PkBandArgs& a = g.a;
+  g.k = 1;
   a.nb = b.nb; a.w = (int32_t)b.w; a.p = (int32_t)b.p; a.ldab = bd_ldab(b.w);
   a.band = b.d_work; a.U = a.band + a.ldab * a.nb; a.C = a.U + a.nb * a.p;
   a.dests = (int64_t)bd_matrix_doubles(b.nb, b.w, b.p);
-  bd_solve_slices(a, b.d_work + a.dests);
+  bd_solve_slices(a, 1, b.d_work + a.dests);
   a.rec = a.bc + a.p;
   a.ipiv = (int32_t*)b.d_ipiv;
   a.map = b.d_map; a.order = b.d_order; a.where = b.d_where;
   a.nh = c->csr[1].n_unique; a.nj = c->csr[0].n_unique; a.ns1 = c->n;
   a.nsol = (int64_t)c->n + c->m;
-  return a;
+  return g;
 }
 
-// ---------------------------------------------------------------- the batch: the same launch sequences with the grid (., B)
-int bd_enqueue_factor_batch(pk_ctx* c, PkBandBatchArgs g, int32_t B, bool fill, hipStream_t st) {
-  const PkBandArgs& a = g.a;
-  PK_LIB_LAUNCH_Y(c, pk_bd_init_bk, bd_init_bhost, 1u, B, st, g);
-  if (fill && a.dests > 0) PK_LIB_LAUNCH_Y(c, pk_bd_fill_bk, bd_fill_bhost, lib_grid(lib_elem_items(a.dests)), B, st, g);
-  for (int64_t j0 = 0; j0 < a.nb; j0 += PK_BD_NB) {
-    g.a.j0 = j0;
-    PK_LIB_LAUNCH_Y(c, pk_bd_panel_bk, bd_panel_bhost, 1u, B, st, g);
-    const int64_t j1 = std::min<int64_t>(j0 + PK_BD_NB, a.nb);
-    const int64_t columns = std::min<int64_t>(j1 - 1 + 2 * (int64_t)a.w, a.nb - 1) - j1 + 1;
-    if (columns > 0) BD_LAUNCH_UPDATE_Y(c, lib_grid(columns), B, st, g, columns);
-  }
-  return 0;
+// the arguments of a raw form, one entry with one column: the caller's arrays and the shape (no fill: the kernels only read U
+// and C)
+PkBandFamilyArgs bd_raw(int64_t nb, int32_t w, int32_t p, double* d_band, const double* d_U, const double* d_C, const double* d_rhs,
+                        int32_t* d_ipiv, double* d_x, double* d_rec) {
+  PkBandFamilyArgs g{};
+  PkBandArgs& a = g.a;
+  g.k = 1;
+  a.nb = nb; a.w = w; a.p = p; a.ldab = bd_ldab(w);
+  a.band = d_band; a.U = const_cast<double*>(d_U); a.C = const_cast<double*>(d_C);
+  a.ipiv = d_ipiv; a.rec = d_rec; a.rhs = d_rhs; a.sol = d_x; a.nsol = nb + p;
+  return g;
 }
 
-int bd_enqueue_solve_batch(pk_ctx* c, PkBandBatchArgs g, int32_t B, hipStream_t st) {
-  const PkBandArgs& a = g.a;
-  if (a.nb + a.p > 0) PK_LIB_LAUNCH_Y(c, pk_bd_prep_bk, bd_prep_bhost, lib_grid(lib_elem_items(a.nb * (a.p + 1) + a.p)), B, st, g);
-  if (a.nb > 0) PK_LIB_LAUNCH_Y(c, pk_bd_solve_bk, bd_solve_bhost, lib_grid((int64_t)a.p + 1), B, st, g);
-  double* from = a.Y;      // (without a border the solution is y_b itself; Y and x move by the same stride)
-  if (a.p > 0) {
-    PK_LIB_LAUNCH_Y(c, pk_bd_dot_bk, bd_dot_bhost, lib_grid((a.p + 1) * a.n_pieces), B, st, g);
-    PK_LIB_LAUNCH_Y(c, pk_bd_border_bk, bd_border_bhost, 1u, B, st, g);
-    if (a.nb > 0) PK_LIB_LAUNCH_Y(c, pk_bd_xb_bk, bd_xb_bhost, lib_grid(lib_elem_items(a.nb)), B, st, g);
-    from = a.x;
-  }
-  g.a.x = from;
-  if (a.nsol > 0) PK_LIB_LAUNCH_Y(c, pk_bd_scatter_bk, bd_scatter_bhost, lib_grid(lib_elem_items(a.nsol)), B, st, g);
-  return 0;
-}
-
+// ---------------------------------------------------------------- the batch
 int bd_batch_size(pk_ctx* c, int32_t B, const char* who) {
   if (B < 1 || B > PK_BD_BATCH_CAP) return fail(c, 134, "%s: a batch of %d (1 ... %d)", who, B, (int)PK_BD_BATCH_CAP);
   return 0;
@@ -1067,14 +811,13 @@ size_t bd_entry_doubles(int64_t nb, int64_t w, int64_t p) { return bd_matrix_dou
 size_t bd_ipiv_doubles(int64_t nb) { return (size_t)nb / 2 + 1; }
 
 // the arguments of B planned systems in the batch's arrays (reserved for at least B)
-PkBandBatchArgs bd_planned_batch(pk_ctx* c, int32_t B) {
+PkBandFamilyArgs bd_planned_batch(pk_ctx* c, int32_t B) {
   const PkBand& b = c->band;
-  PkBandBatchArgs g{};
+  PkBandFamilyArgs g = bd_planned(c);
   PkBandArgs& a = g.a;
-  a = bd_planned(c);
   const int64_t per = (int64_t)bd_entry_doubles(b.nb, b.w, b.p);
   a.band = b.d_bwork; a.U = a.band + a.ldab * a.nb; a.C = a.U + a.nb * a.p;
-  bd_solve_slices(a, b.d_bwork + a.dests);
+  bd_solve_slices(a, 1, b.d_bwork + a.dests);
   a.rec = b.d_bwork + per * B;
   a.ipiv = (int32_t*)b.d_bipiv;
   g.s_band = g.s_U = g.s_C = g.s_work = per;
@@ -1083,7 +826,7 @@ PkBandBatchArgs bd_planned_batch(pk_ctx* c, int32_t B) {
   return g;
 }
 
-int bd_partial_batch(pk_ctx* c, PkBandBatchArgs& g, int32_t B, const char* who) {
+int bd_partial_batch(pk_ctx* c, PkBandFamilyArgs& g, int32_t B, const char* who) {
   PkBandArgs& a = g.a;
   a.n_pieces = lib_dot_pieces(a.nb);
   const size_t per = (size_t)(a.p + 1) * (size_t)a.p * (size_t)a.n_pieces;
@@ -1096,30 +839,13 @@ int bd_partial_batch(pk_ctx* c, PkBandBatchArgs& g, int32_t B, const char* who) 
 }
 
 // ---------------------------------------------------------------- the block: k right-hand sides behind one factorisation
-// the launches of ONE solve (3 without a border, 6 with one); the arguments hold everything but the scatter's source
-int bd_enqueue_solve_multi(pk_ctx* c, PkBandMultiArgs g, hipStream_t st) {
-  const PkBandArgs& a = g.a;
-  const int64_t k = g.k, N = a.nb + a.p;
-  if (N > 0) PK_LIB_LAUNCH(c, pk_bd_mprep_k, bd_mprep_host, lib_grid(lib_elem_items(a.nb * a.p + k * N)), st, g);
-  if (a.nb > 0) PK_LIB_LAUNCH(c, pk_bd_msolve_k, bd_msolve_host, lib_grid((int64_t)a.p + k), st, g);
-  g.from = a.Y; g.s_from = a.nb;      // (without a border the solutions are the swept right-hand sides themselves)
-  if (a.p > 0) {
-    PK_LIB_LAUNCH(c, pk_bd_mdot_k, bd_mdot_host, lib_grid(((int64_t)a.p + k) * a.n_pieces), st, g);
-    PK_LIB_LAUNCH(c, pk_bd_mborder_k, bd_mborder_host, 1u, st, g);
-    if (a.nb > 0) PK_LIB_LAUNCH(c, pk_bd_mxb_k, bd_mxb_host, lib_grid(lib_elem_items(k * a.nb)), st, g);
-    g.from = a.x; g.s_from = N;
-  }
-  if (a.nsol > 0) PK_LIB_LAUNCH(c, pk_bd_mscatter_k, bd_mscatter_host, lib_grid(lib_elem_items(k * a.nsol)), st, g);
-  return 0;
-}
-
 int bd_rhs_count(pk_ctx* c, int32_t k, const char* who) {
   if (k < 1 || k > PK_BD_RHS_CAP) return fail(c, 134, "%s: a block of %d right-hand sides (1 ... %d)", who, k, (int)PK_BD_RHS_CAP);
   return 0;
 }
 
-// the block's work arrays for k right-hand sides of the shape in g.a, and its slices into the arguments
-int bd_multi_work(pk_ctx* c, PkBandMultiArgs& g, const char* who) {
+// the block's work arrays for g.k right-hand sides of the shape in g.a, and its slices into the arguments
+int bd_multi_work(pk_ctx* c, PkBandFamilyArgs& g, const char* who) {
   PkBandArgs& a = g.a;
   PkBand& b = c->band;
   const size_t k = (size_t)g.k, nb = (size_t)a.nb, p = (size_t)a.p;
@@ -1133,16 +859,31 @@ int bd_multi_work(pk_ctx* c, PkBandMultiArgs& g, const char* who) {
     if ((rc = lib_reserve(c, b.d_mpartial, b.mpartial_cap, (p + k) * p * (size_t)a.n_pieces, 136, who, named))) return rc;
   }
   a.partial = p > 0 ? b.d_mpartial : nullptr;
-  a.Y = b.d_mwork;
-  a.x = a.Y + (p + k) * nb;
-  a.bc = a.x + k * (nb + p);
+  bd_solve_slices(a, g.k, b.d_mwork);
   return 0;
 }
 
-int bd_batch_planned(pk_ctx* c, const char* who) {
+// ---------------------------------------------------------------- the host forms of one system: k right-hand sides
+// Behind the caller's own refusals: the plan, the linearization, then b and [s1 | s2] up into `scratch` ([b | s1 | s2 | x], named
+// `what` in error 136), the factorisation, solve(d_b, d_x), and x back where the record says solved.  The batch's host form
+// is not folded in: it has B rows of s1 and s2 at strides of their own, B records and a copy-back per entry's status.
+template <class Solve>
+int bd_host_form(pk_ctx* c, const char* who, size_t k, double*& scratch, size_t& cap, const char* what, const double* s1, const double* s2,
+                 const double* b, double* x, double* rec, Solve solve) {
+  const double *jvals = nullptr, *hvals = nullptr;
+  int rc;
   if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
-  if (c->band.sources != c->csr[1].n_unique + c->csr[0].n_unique + (int64_t)c->n + c->m)
-    return fail(c, 134, "%s: the CSR maps changed since pk_band_plan", who);
+  if ((rc = solve_linearized(c, true, jvals, hvals, who))) return rc;
+  const size_t n = (size_t)c->n, m = (size_t)c->m, N = n + m;
+  if ((rc = lib_reserve(c, scratch, cap, (2 * k + 1) * N + 1, 136, who, what))) return rc;
+  double *d_b = scratch, *d_s = d_b + N * k, *d_x = d_s + N;
+  PK_HIP(c, hipSetDevice(c->device));
+  if ((rc = lib_upload(c, d_b, b, N * k)) || (rc = lib_upload(c, d_s, s1, n)) || (rc = lib_upload(c, d_s + n, s2, m))) return rc;
+  if ((rc = pk_band_factor_dev(c, hvals, jvals, d_s, d_s + n)) || (rc = solve(d_b, d_x))) return rc;
+  std::vector<double> got(N * k + 1);
+  if (N) PK_HIP(c, hipMemcpyAsync(got.data(), d_x, sizeof(double) * N * k, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = pk_band_record(c, rec))) return rc;      // (synchronises)
+  if (rec[BD_STATUS] == 0.0) std::copy(got.begin(), got.begin() + (long)(N * k), x);
   return 0;
 }
 
@@ -1203,13 +944,10 @@ int pk_band_factor_dev(pk_ctx* c, const double* d_hvals, const double* d_jvals, 
   int rc = ready(c);
   if (rc) return rc;
   if (!d_hvals || !d_jvals || !d_s1 || !d_s2) return fail(c, 110, "%s: null device pointer", who);
-  if ((rc = bd_context(c, who))) return rc;
-  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
-  if (c->band.sources != c->csr[1].n_unique + c->csr[0].n_unique + (int64_t)c->n + c->m)
-    return fail(c, 134, "%s: the CSR maps changed since pk_band_plan", who);
-  PkBandArgs a = bd_planned(c);
-  a.hvals = d_hvals; a.jvals = d_jvals; a.s1 = d_s1; a.s2 = d_s2;
-  if ((rc = bd_enqueue_factor(c, a, true, c->stream))) return rc;
+  if ((rc = bd_context(c, who)) || (rc = bd_plan_current(c, who))) return rc;
+  PkBandFamilyArgs g = bd_planned(c);
+  g.a.hvals = d_hvals; g.a.jvals = d_jvals; g.a.s1 = d_s1; g.a.s2 = d_s2;
+  if ((rc = bd_enqueue_factor(c, g, 1, true, c->stream))) return rc;
   c->band.factored = true;
   return 0;
 }
@@ -1221,10 +959,10 @@ int pk_band_solve_dev(pk_ctx* c, const double* d_rhs, double* d_sol) {
   if (!d_rhs || !d_sol) return fail(c, 110, "%s: null device pointer", who);
   if ((rc = bd_context(c, who))) return rc;
   if (!c->band.planned || !c->band.factored) return fail(c, 134, "%s: no factorisation (pk_band_plan, pk_band_factor_dev)", who);
-  PkBandArgs a = bd_planned(c);
-  if ((rc = bd_partial(c, a, who))) return rc;
-  a.rhs = d_rhs; a.sol = d_sol;
-  return bd_enqueue_solve(c, a, c->stream);
+  PkBandFamilyArgs g = bd_planned(c);
+  if ((rc = bd_partial(c, g.a, who))) return rc;
+  g.a.rhs = d_rhs; g.a.sol = d_sol;
+  return bd_enqueue_solve(c, g, 1, c->stream);
 }
 
 int pk_band_solve_multi_dev(pk_ctx* c, int32_t k, const double* d_rhs, int64_t stride_rhs, double* d_sol, int64_t stride_sol) {
@@ -1237,12 +975,11 @@ int pk_band_solve_multi_dev(pk_ctx* c, int32_t k, const double* d_rhs, int64_t s
   const int64_t N = (int64_t)c->n + c->m;
   if ((rc = bd_stride(c, stride_rhs, N, false, who, "the right-hand sides")) || (rc = bd_stride(c, stride_sol, N, false, who, "the solutions")))
     return rc;
-  PkBandMultiArgs g{};
-  g.a = bd_planned(c);      // (the matrix, ipiv, order, where and the record; the work slices are the block's own)
-  g.k = k; g.s_rhs = stride_rhs; g.s_sol = stride_sol;
+  PkBandFamilyArgs g = bd_planned(c);      // (the matrix, ipiv, order, where and the record; the work slices are the block's own)
+  g.k = k; g.c_rhs = stride_rhs; g.c_sol = stride_sol;
   if ((rc = bd_multi_work(c, g, who))) return rc;
   g.a.rhs = d_rhs; g.a.sol = d_sol;
-  return bd_enqueue_solve_multi(c, g, c->stream);
+  return bd_enqueue_solve(c, g, 1, c->stream);
 }
 
 int pk_band_record(pk_ctx* c, double* rec) {
@@ -1251,7 +988,7 @@ int pk_band_record(pk_ctx* c, double* rec) {
   if (rc) return rc;
   if (!rec) return fail(c, 60, "null host buffer");
   if (!c->band.planned || !c->band.factored) return fail(c, 134, "%s: no factorisation (pk_band_plan, pk_band_factor_dev)", who);
-  const PkBandArgs a = bd_planned(c);
+  const PkBandArgs a = bd_planned(c).a;
   PK_HIP(c, hipSetDevice(c->device));
   PK_HIP(c, hipMemcpyAsync(rec, a.rec, sizeof(double) * PK_BD_REC, hipMemcpyDeviceToHost, c->stream));
   PK_HIP(c, hipStreamSynchronize(c->stream));
@@ -1260,42 +997,19 @@ int pk_band_record(pk_ctx* c, double* rec) {
 
 int pk_solve_banded(pk_ctx* c, const double* s1, const double* s2, const double* b, double* x, double* rec) {
   const char* who = "pk_solve_banded";
-  const double *jvals = nullptr, *hvals = nullptr;
   int rc = host_ready(c, s1 && s2 && b && x && rec);
   if (rc || (rc = solve_ops_ready(c, true, true, who))) return rc;
-  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
-  if ((rc = solve_linearized(c, true, jvals, hvals, who))) return rc;
-  const size_t n = (size_t)c->n, m = (size_t)c->m, N = n + m;
-  if ((rc = lib_reserve(c, c->band.d_scratch, c->band.scratch_cap, 3 * N + 1, 136, who, "host-form scratch"))) return rc;
-  double *d_b = c->band.d_scratch, *d_s = d_b + N, *d_x = d_s + N;
-  PK_HIP(c, hipSetDevice(c->device));
-  if ((rc = lib_upload(c, d_b, b, N)) || (rc = lib_upload(c, d_s, s1, n)) || (rc = lib_upload(c, d_s + n, s2, m))) return rc;
-  if ((rc = pk_band_factor_dev(c, hvals, jvals, d_s, d_s + n)) || (rc = pk_band_solve_dev(c, d_b, d_x))) return rc;
-  std::vector<double> got(N + 1);
-  if (N) PK_HIP(c, hipMemcpyAsync(got.data(), d_x, sizeof(double) * N, hipMemcpyDeviceToHost, c->stream));
-  if ((rc = pk_band_record(c, rec))) return rc;      // (synchronises)
-  if (rec[BD_STATUS] == 0.0) std::copy(got.begin(), got.begin() + (long)N, x);
-  return 0;
+  return bd_host_form(c, who, 1, c->band.d_scratch, c->band.scratch_cap, "host-form scratch", s1, s2, b, x, rec,
+                      [&](const double* d_b, double* d_x) { return pk_band_solve_dev(c, d_b, d_x); });
 }
 
 int pk_solve_banded_multi(pk_ctx* c, int32_t k, const double* s1, const double* s2, const double* b, double* x, double* rec) {
   const char* who = "pk_solve_banded_multi";
-  const double *jvals = nullptr, *hvals = nullptr;
   int rc = host_ready(c, s1 && s2 && b && x && rec);
   if (rc || (rc = solve_ops_ready(c, true, true, who)) || (rc = bd_rhs_count(c, k, who))) return rc;
-  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
-  if ((rc = solve_linearized(c, true, jvals, hvals, who))) return rc;
-  const size_t n = (size_t)c->n, m = (size_t)c->m, N = n + m, nk = (size_t)k;
-  if ((rc = lib_reserve(c, c->band.d_mscratch, c->band.mscratch_cap, (2 * nk + 1) * N + 1, 136, who, "host-form scratch of the block"))) return rc;
-  double *d_b = c->band.d_mscratch, *d_s = d_b + N * nk, *d_x = d_s + N;
-  PK_HIP(c, hipSetDevice(c->device));
-  if ((rc = lib_upload(c, d_b, b, N * nk)) || (rc = lib_upload(c, d_s, s1, n)) || (rc = lib_upload(c, d_s + n, s2, m))) return rc;
-  if ((rc = pk_band_factor_dev(c, hvals, jvals, d_s, d_s + n)) || (rc = pk_band_solve_multi_dev(c, k, d_b, (int64_t)N, d_x, (int64_t)N))) return rc;
-  std::vector<double> got(N * nk + 1);
-  if (N) PK_HIP(c, hipMemcpyAsync(got.data(), d_x, sizeof(double) * N * nk, hipMemcpyDeviceToHost, c->stream));
-  if ((rc = pk_band_record(c, rec))) return rc;      // (synchronises)
-  if (rec[BD_STATUS] == 0.0) std::copy(got.begin(), got.begin() + (long)(N * nk), x);
-  return 0;
+  const int64_t N = (int64_t)c->n + c->m;
+  return bd_host_form(c, who, (size_t)k, c->band.d_mscratch, c->band.mscratch_cap, "host-form scratch of the block", s1, s2, b, x, rec,
+                      [&](const double* d_b, double* d_x) { return pk_band_solve_multi_dev(c, k, d_b, N, d_x, N); });
 }
 
 int pk_band_factor_batch_dev(pk_ctx* c, int32_t B, const double* d_hvals, int64_t stride_h, const double* d_jvals, int64_t stride_j,
@@ -1304,7 +1018,7 @@ int pk_band_factor_batch_dev(pk_ctx* c, int32_t B, const double* d_hvals, int64_
   int rc = ready(c);
   if (rc) return rc;
   if (!d_hvals || !d_jvals || !d_s1 || !d_s2) return fail(c, 110, "%s: null device pointer", who);
-  if ((rc = bd_context(c, who)) || (rc = bd_batch_size(c, B, who)) || (rc = bd_batch_planned(c, who))) return rc;
+  if ((rc = bd_context(c, who)) || (rc = bd_batch_size(c, B, who)) || (rc = bd_plan_current(c, who))) return rc;
   if ((rc = bd_stride(c, stride_h, c->csr[1].n_unique, true, who, "the Hessian's values")) ||
       (rc = bd_stride(c, stride_j, c->csr[0].n_unique, true, who, "the Jacobian's values")) ||
       (rc = bd_stride(c, stride_s1, c->n, true, who, "s1")) || (rc = bd_stride(c, stride_s2, c->m, true, who, "s2")))
@@ -1314,11 +1028,11 @@ int pk_band_factor_batch_dev(pk_ctx* c, int32_t B, const double* d_hvals, int64_
                              "the bands, the borders and the right-hand sides")) ||
       (rc = bd_batch_reserve(c, b.d_bipiv, b.bipiv_cap, bd_ipiv_doubles(b.nb), B, true, who, "the interchanges")))
     return rc;
-  PkBandBatchArgs g = bd_planned_batch(c, B);
+  PkBandFamilyArgs g = bd_planned_batch(c, B);
   g.a.hvals = d_hvals; g.a.jvals = d_jvals; g.a.s1 = d_s1; g.a.s2 = d_s2;
   g.s_h = stride_h; g.s_j = stride_j; g.s_s1 = stride_s1; g.s_s2 = stride_s2;
   b.batch = 0;      // (the factors of an earlier batch are overwritten from here on)
-  if ((rc = bd_enqueue_factor_batch(c, g, B, true, c->stream))) return rc;
+  if ((rc = bd_enqueue_factor(c, g, B, true, c->stream))) return rc;
   b.batch = B;
   return 0;
 }
@@ -1335,11 +1049,11 @@ int pk_band_solve_batch_dev(pk_ctx* c, int32_t B, const double* d_rhs, int64_t s
   const int64_t N = (int64_t)c->n + c->m;
   if ((rc = bd_stride(c, stride_rhs, N, true, who, "the right-hand sides")) || (rc = bd_stride(c, stride_sol, N, false, who, "the solutions")))
     return rc;
-  PkBandBatchArgs g = bd_planned_batch(c, B);
+  PkBandFamilyArgs g = bd_planned_batch(c, B);
   if ((rc = bd_partial_batch(c, g, B, who))) return rc;
   g.a.rhs = d_rhs; g.a.sol = d_sol;
   g.s_rhs = stride_rhs; g.s_sol = stride_sol;
-  return bd_enqueue_solve_batch(c, g, B, c->stream);
+  return bd_enqueue_solve(c, g, B, c->stream);
 }
 
 int pk_band_record_batch(pk_ctx* c, int32_t B, double* rec) {
@@ -1351,7 +1065,7 @@ int pk_band_record_batch(pk_ctx* c, int32_t B, double* rec) {
   if (!c->band.planned || c->band.batch != B)
     return fail(c, 134, "%s: no batch factorisation of %d entries (pk_band_plan, pk_band_factor_batch_dev; the last one had %d)", who, B,
                 (int)c->band.batch);
-  const PkBandBatchArgs g = bd_planned_batch(c, B);
+  const PkBandFamilyArgs g = bd_planned_batch(c, B);
   PK_HIP(c, hipSetDevice(c->device));
   PK_HIP(c, hipMemcpyAsync(rec, g.a.rec, sizeof(double) * PK_BD_REC * (size_t)B, hipMemcpyDeviceToHost, c->stream));      // (the records are one array)
   PK_HIP(c, hipStreamSynchronize(c->stream));
@@ -1388,14 +1102,11 @@ int pk_band_fill_dev(pk_ctx* c, const double* d_hvals, const double* d_jvals, co
   int rc = ready(c);
   if (rc) return rc;
   if (!d_hvals || !d_jvals || !d_s1 || !d_s2 || !d_out) return fail(c, 110, "%s: null device pointer", who);
-  if ((rc = bd_context(c, who))) return rc;
-  if (!c->band.planned) return fail(c, 134, "%s: no plan (pk_band_plan)", who);
-  if (c->band.sources != c->csr[1].n_unique + c->csr[0].n_unique + (int64_t)c->n + c->m)
-    return fail(c, 134, "%s: the CSR maps changed since pk_band_plan", who);
-  PkBandArgs a = bd_planned(c);
-  a.hvals = d_hvals; a.jvals = d_jvals; a.s1 = d_s1; a.s2 = d_s2;
-  a.band = d_out;      // (band, U and C are one array: the caller's)
-  if (a.dests > 0) PK_LIB_LAUNCH(c, pk_bd_fill_k, bd_fill_host, lib_grid(lib_elem_items(a.dests)), c->stream, a);
+  if ((rc = bd_context(c, who)) || (rc = bd_plan_current(c, who))) return rc;
+  PkBandFamilyArgs g = bd_planned(c);
+  g.a.hvals = d_hvals; g.a.jvals = d_jvals; g.a.s1 = d_s1; g.a.s2 = d_s2;
+  g.a.band = d_out;      // (band, U and C are one array: the caller's)
+  if (g.a.dests > 0) PK_LIB_LAUNCH_Y(c, pk_bd_fill_k, bd_fill_host, lib_grid(lib_elem_items(g.a.dests)), 1, c->stream, g);
   return 0;
 }
 
@@ -1407,15 +1118,12 @@ int pk_band_raw_dev(pk_ctx* c, int64_t nb, int32_t w, int32_t p, int32_t R, doub
   if (!d_band || !d_rhs || !d_ipiv || !d_x || !d_rec || (p > 0 && (!d_U || !d_C))) return fail(c, 110, "%s: null device pointer", who);
   if ((rc = bd_shape(c, nb, w, p, who))) return rc;
   if (R != p + 1) return fail(c, 134, "%s: R = %d right-hand sides for a border of %d (p + 1: the border's columns and b)", who, R, p);
-  PkBandArgs a{};
-  a.nb = nb; a.w = w; a.p = p; a.ldab = bd_ldab(w);
-  a.band = d_band; a.U = const_cast<double*>(d_U); a.C = const_cast<double*>(d_C);      // (no fill: the kernels read them only)
-  a.ipiv = d_ipiv; a.rec = d_rec; a.rhs = d_rhs; a.sol = d_x; a.nsol = nb + p;
-  if ((rc = lib_reserve(c, c->band.d_raw, c->band.raw_cap, bd_solve_doubles(nb, p), 136, who, "the right-hand sides")) || (rc = bd_partial(c, a, who)))
+  PkBandFamilyArgs g = bd_raw(nb, w, p, d_band, d_U, d_C, d_rhs, d_ipiv, d_x, d_rec);
+  if ((rc = lib_reserve(c, c->band.d_raw, c->band.raw_cap, bd_solve_doubles(nb, p), 136, who, "the right-hand sides")) || (rc = bd_partial(c, g.a, who)))
     return rc;
-  bd_solve_slices(a, c->band.d_raw);
-  if ((rc = bd_enqueue_factor(c, a, false, c->stream))) return rc;
-  return bd_enqueue_solve(c, a, c->stream);
+  bd_solve_slices(g.a, 1, c->band.d_raw);
+  if ((rc = bd_enqueue_factor(c, g, 1, false, c->stream))) return rc;
+  return bd_enqueue_solve(c, g, 1, c->stream);
 }
 
 int pk_band_raw_multi_dev(pk_ctx* c, int64_t nb, int32_t w, int32_t p, int32_t k, double* d_band, const double* d_U, const double* d_C,
@@ -1427,15 +1135,11 @@ int pk_band_raw_multi_dev(pk_ctx* c, int64_t nb, int32_t w, int32_t p, int32_t k
   if ((rc = bd_shape(c, nb, w, p, who)) || (rc = bd_rhs_count(c, k, who))) return rc;
   if ((rc = bd_stride(c, stride_rhs, nb + p, false, who, "the right-hand sides")) || (rc = bd_stride(c, stride_x, nb + p, false, who, "the solutions")))
     return rc;
-  PkBandMultiArgs g{};
-  PkBandArgs& a = g.a;
-  a.nb = nb; a.w = w; a.p = p; a.ldab = bd_ldab(w);
-  a.band = d_band; a.U = const_cast<double*>(d_U); a.C = const_cast<double*>(d_C);      // (no fill: the kernels read them only)
-  a.ipiv = d_ipiv; a.rec = d_rec; a.rhs = d_rhs; a.sol = d_x; a.nsol = nb + p;
-  g.k = k; g.s_rhs = stride_rhs; g.s_sol = stride_x;
+  PkBandFamilyArgs g = bd_raw(nb, w, p, d_band, d_U, d_C, d_rhs, d_ipiv, d_x, d_rec);
+  g.k = k; g.c_rhs = stride_rhs; g.c_sol = stride_x;
   if ((rc = bd_multi_work(c, g, who))) return rc;
-  if ((rc = bd_enqueue_factor(c, a, false, c->stream))) return rc;
-  return bd_enqueue_solve_multi(c, g, c->stream);
+  if ((rc = bd_enqueue_factor(c, g, 1, false, c->stream))) return rc;
+  return bd_enqueue_solve(c, g, 1, c->stream);
 }
 
 int pk_band_raw_batch_dev(pk_ctx* c, int32_t B, int64_t nb, int32_t w, int32_t p, int32_t R, double* d_band, int64_t stride_band,
@@ -1452,20 +1156,16 @@ int pk_band_raw_batch_dev(pk_ctx* c, int32_t B, int64_t nb, int32_t w, int32_t p
       (rc = bd_stride(c, stride_ipiv, nb, false, who, "the interchanges")) || (rc = bd_stride(c, stride_x, nb + p, false, who, "the solutions")) ||
       (rc = bd_stride(c, stride_rec, PK_BD_REC, false, who, "the records")))
     return rc;
-  PkBandBatchArgs g{};
-  PkBandArgs& a = g.a;
-  a.nb = nb; a.w = w; a.p = p; a.ldab = bd_ldab(w);
-  a.band = d_band; a.U = const_cast<double*>(d_U); a.C = const_cast<double*>(d_C);      // (no fill: the kernels read them only)
-  a.ipiv = d_ipiv; a.rec = d_rec; a.rhs = d_rhs; a.sol = d_x; a.nsol = nb + p;
+  PkBandFamilyArgs g = bd_raw(nb, w, p, d_band, d_U, d_C, d_rhs, d_ipiv, d_x, d_rec);
   g.s_band = stride_band; g.s_U = d_U ? stride_U : 0; g.s_C = d_C ? stride_C : 0; g.s_rhs = stride_rhs;
   g.s_ipiv = stride_ipiv; g.s_sol = stride_x; g.s_rec = stride_rec;
   g.s_work = (int64_t)bd_solve_doubles(nb, p);
   if ((rc = bd_batch_reserve(c, c->band.d_braw, c->band.braw_cap, (size_t)g.s_work, B, false, who, "the right-hand sides")) ||
       (rc = bd_partial_batch(c, g, B, who)))
     return rc;
-  bd_solve_slices(a, c->band.d_braw);
-  if ((rc = bd_enqueue_factor_batch(c, g, B, false, c->stream))) return rc;
-  return bd_enqueue_solve_batch(c, g, B, c->stream);
+  bd_solve_slices(g.a, 1, c->band.d_braw);
+  if ((rc = bd_enqueue_factor(c, g, B, false, c->stream))) return rc;
+  return bd_enqueue_solve(c, g, B, c->stream);
 }
 
 }  // extern "C"

@@ -23,8 +23,8 @@
 //                   pk_sl_update_k, pk_sl_merit_k, pk_sl_scalar_k: the library's own kernels)
 //   pk_band.cpp     the step's system assembled, factored and solved on the device: a band LU with partial pivoting inside the
 //                   band, bordered by the few dense unknowns (pk_bd_init_k, pk_bd_fill_k, pk_bd_panel_k, pk_bd_update_k,
-//                   pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k, their batch forms pk_bd_*_bk and
-//                   the block solve's pk_bd_mprep_k ... pk_bd_mscatter_k: the library's own kernels)
+//                   pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k: the library's own kernels, one
+//                   family for a single system, a batch of entries and a block of right-hand sides)
 //   pk_solve.cpp    the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp: the context's growing
 //                   arrays (lib_reserve, also pk_merit.cpp's, pk_ipm.cpp's, pk_slack.cpp's and pk_band.cpp's), the common checks, the skeletons of record / advance / the host loop
 //   pk_error.cpp    fail(): where an error message is kept

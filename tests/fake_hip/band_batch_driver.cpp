@@ -1,92 +1,35 @@
 // band_batch_driver.cpp -- TEST INFRASTRUCTURE: drives the BATCH forms of pockit_amd/csrc/pk_band.cpp (B step systems behind one
 // plan, factored and solved in one launch sequence) against the host-only HIP stand-in of this directory, built with
 // -fsanitize=address,undefined (tests/test_band_batch_cpu.py).  The contract is that entry e of a batch has, bit for bit, what the
-// single form gives for entry e's inputs alone, so the reference here is the SINGLE raw form (which tests/fake_hip/band_driver.cpp
-// holds against plain loops): the raw batch form at B = 1, 2, 3, 16 on full-mantissa data, every array packed at a stride larger
+// single form gives for entry e's inputs alone.  The single raw form runs the same kernels as a batch of one, so every entry of
+// a shape is held twice: to the SINGLE raw form (entry e of B equals entry 0 of 1) and to the PLAIN LOOPS of band_driver_common.h
+// (band inside the matrix and fill rows, interchanges, solution, record): the raw batch form at B = 1, 2, 3, 16 on full-mantissa data, every array packed at a stride larger
 // than its length with NaN in the gaps (still NaN afterwards); a batch with a zero column and a planted NaN among good entries;
 // a batch against itself permuted; shared sources (stride 0) against the same array repeated; the planned forms at B = 2, 5, 2
 // with a single factorisation in between that keeps its bits; the host form against the device forms; every refusal with its
 // code and nothing enqueued or written; tear-down without a live allocation.  With --dump FILE: the batch FILE describes
 // (tests/test_band_batch_cpu.py writes it from tests/band_batch_cases.py) through the raw batch form, per entry band,
 // interchanges, solution and record printed as hex doubles.
-#include <cmath>
-#include <cstring>
+#include "band_driver_common.h"
 
-#include "driver_common.h"
+enum { GAP = 3 };
 
-enum { NB = 32, W_CAP = 192, P_CAP = 8, BATCH_CAP = 16, REC = 8, GAP = 3 };
-enum { STATUS = 0, COLUMN = 1 };
-enum { PLAIN = 0, TINY = 1, ZERO = 2, PLANT = 3 };
-enum { EVERY = 70 };      // up to this Nb the tiny diagonal comes with a dominant subdiagonal: every column but the last interchanges
-
-// ---------------------------------------------------------------- synthetic systems of full-mantissa values
-static uint64_t g_state = 1;
-static double unit() {      // in (-1, 1), 53 random bits
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  const double v = (double)(g_state >> 11) * 0x1p-53;
-  return 2.0 * v - 1.0;
+// (the seed's term for a variant is this driver's own number of it: zero column 2, planted NaN 3)
+static Sys make(int64_t nb, int w, int p, Variant variant, int salt) {
+  const uint64_t code = variant == ZERO ? 2 : variant == PLANT ? 3 : (uint64_t)variant;
+  return make_system(nb, w, p, variant, code, (uint64_t)salt, 1, 0);
 }
 
-struct Sys {
-  int64_t nb = 0;
-  int w = 0, p = 0;
-  int64_t ldab = 1;
-  Vec band, U, C, rhs;      // band: NaN in the fill rows and outside the matrix
-  double& at(int64_t i, int64_t j) { return band[(size_t)((2 * (int64_t)w + i - j) + j * ldab)]; }
-};
-
-static Sys make(int64_t nb, int w, int p, int variant, int salt) {
-  g_state = 1000003ull * (uint64_t)nb + 7919ull * (uint64_t)w + 31ull * (uint64_t)p + (uint64_t)variant + 104729ull * (uint64_t)salt;
-  Sys s;
-  s.nb = nb; s.w = w; s.p = p; s.ldab = 3 * (int64_t)w + 1;
-  s.band = made((size_t)(s.ldab * nb));
-  std::fill(s.band.begin(), s.band.end(), NAN);
-  for (int64_t j = 0; j < nb; ++j)
-    for (int64_t i = std::max<int64_t>(0, j - w); i <= std::min<int64_t>(nb - 1, j + w); ++i) s.at(i, j) = unit();
-  for (int64_t j = 0; j < nb; ++j) {
-    const double d = (1.5 + 0.5 * unit()) * (unit() < 0.0 ? -1.0 : 1.0) * (0.25 * w + 1.0);
-    s.at(j, j) = variant == TINY ? d * 0x1p-26 : d;
-    if (variant == TINY && w > 0 && nb <= EVERY && j + 1 < nb) s.at(j + 1, j) = s.at(j + 1, j) * 1024.0 + (s.at(j + 1, j) < 0.0 ? -1024.0 : 1024.0);
-  }
-  if (variant == ZERO && nb) {
-    const int64_t j = 2 * nb / 3;
-    for (int64_t i = std::max<int64_t>(0, j - w); i <= std::min<int64_t>(nb - 1, j + w); ++i) s.at(i, j) = 0.0;
-  }
-  if (variant == PLANT && nb) s.at(nb / 2, nb / 2) = NAN;
-  s.U = made((size_t)(nb * p)); s.C = made((size_t)(p * p)); s.rhs = made((size_t)(nb + p));
-  for (double& v : s.U) v = unit();
-  for (double& v : s.C) v = unit();
-  for (int k = 0; k < p; ++k) s.C[(size_t)(k + k * p)] += 4.0 + p;
-  for (double& v : s.rhs) v = unit();
-  return s;
-}
-
-// ---------------------------------------------------------------- one system through the single raw form
-struct Got {
-  Vec band, x, rec;
-  std::vector<int32_t> ipiv;
-};
-
-static bool same_or_nan(const double* a, const double* b, size_t count) {
-  for (size_t i = 0; i < count; ++i)
-    if (std::memcmp(a + i, b + i, 8) != 0 && !(std::isnan(a[i]) && std::isnan(b[i]))) return false;
-  return true;
-}
 static bool all_nan(const double* a, size_t count) {
   for (size_t i = 0; i < count; ++i)
     if (!std::isnan(a[i])) return false;
   return true;
 }
 
+// one system through the single raw form
 static Got single(const Sys& s) {
   Got g;
-  g.band = s.band;
-  g.band.reserve(g.band.size() + 1);
-  g.x = made((size_t)(s.nb + s.p)); g.rec = made(REC);
-  std::fill(g.x.begin(), g.x.end(), -77.0); std::fill(g.rec.begin(), g.rec.end(), -77.0);
-  g.ipiv.assign((size_t)s.nb + 1, -7);
-  OK(pk_band_raw_dev(ctx, s.nb, s.w, s.p, s.p + 1, g.band.data(), s.U.data(), s.C.data(), s.rhs.data(), g.ipiv.data(), g.x.data(), g.rec.data()));
-  OK(pk_sync(ctx, nullptr));
+  OK(raw_single(s, 0, g));
   return g;
 }
 
@@ -139,7 +82,8 @@ static int run(Batch& b) {
 // entry e of the batch has the single form's bits in band, interchanges, solution and record
 static bool entry_matches(const Batch& b, int e, const Got& g) {
   if (!same_or_nan(b.band.data() + b.stride(b.l_band) * e, g.band.data(), (size_t)b.l_band)) return false;
-  if (b.nb && std::memcmp(b.ipiv.data() + b.stride(b.nb) * e, g.ipiv.data(), 4 * (size_t)b.nb) != 0) return false;
+  for (int64_t j = 0; j < b.nb; ++j)
+    if ((double)b.ipiv[(size_t)(b.stride(b.nb) * e + j)] != g.ipiv[(size_t)j]) return false;
   if (b.l_v && std::memcmp(b.x.data() + b.stride(b.l_v) * e, g.x.data(), 8 * (size_t)b.l_v) != 0) return false;
   return std::memcmp(b.rec.data() + b.stride(REC) * e, g.rec.data(), 8 * REC) == 0;
 }
@@ -154,6 +98,22 @@ static bool gaps_intact(const Batch& b) {
       if (b.ipiv[(size_t)(b.stride(b.nb) * e + b.nb + k)] != -9) return false;
   }
   return true;
+}
+
+// entry e of the batch has the bits of the plain loops: the record; behind a solve the band inside the matrix and in the fill
+// rows, the interchanges and the solution; behind a failure the solution untouched
+static bool entry_is_reference(const Batch& b, int e, const Sys& s, const Ref& want) {
+  if (std::memcmp(b.rec.data() + b.stride(REC) * e, want.rec.data(), 8 * REC) != 0) return false;
+  const double* x = b.x.data() + b.stride(b.l_v) * e;
+  if (want.rec[STATUS] != 0.0) {
+    for (int64_t i = 0; i < b.l_v; ++i)
+      if (x[i] != -77.0) return false;
+    return true;
+  }
+  if (!band_matches(s, b.band.data() + b.stride(b.l_band) * e, want.band)) return false;
+  for (int64_t j = 0; j < b.nb; ++j)
+    if (b.ipiv[(size_t)(b.stride(b.nb) * e + j)] != want.ipiv[(size_t)j]) return false;
+  return b.l_v == 0 || std::memcmp(x, want.x[0].data(), 8 * (size_t)b.l_v) == 0;
 }
 
 static double status_of(const Batch& b, int e) { return b.rec[(size_t)(b.stride(REC) * e + STATUS)]; }
@@ -171,16 +131,15 @@ static void check_shape(int B, int64_t nb, int w, int p) {
   Batch b = pack(entries);
   OK(run(b));
   for (int e = 0; e < B; ++e) {
-    const Got g = single(entries[(size_t)e]);
+    const Got g = single(entries[(size_t)e]);      // entry e of B equals entry 0 of 1 ...
     if (!entry_matches(b, e, g)) std::fprintf(stderr, "B %d nb %d w %d p %d: entry %d\n", g_B, g_nb, g_w, g_p, e);
     CHECK(entry_matches(b, e, g));
+    const Ref want = reference(entries[(size_t)e]);      // ... and both are the plain loops
+    if (!entry_is_reference(b, e, entries[(size_t)e], want)) std::fprintf(stderr, "B %d nb %d w %d p %d: entry %d against the plain loops\n", g_B, g_nb, g_w, g_p, e);
+    CHECK(entry_is_reference(b, e, entries[(size_t)e], want));
     if (e % 2 == 0) CHECK(status_of(b, e) == 0.0);      // (a tiny diagonal may leave a border that is singular in fp64: the bits still agree)
   }
   CHECK(gaps_intact(b));
-}
-
-static void print(const double* v, int64_t count) {
-  for (int64_t i = 0; i < count; ++i) std::printf("%a\n", v[i]);
 }
 
 // FILE: "B nb w p", then per entry band (ldab x nb, column-major), U, C, rhs
@@ -192,7 +151,7 @@ static int dump(const char* path) {
   if (std::fscanf(f, "%d %lld %d %d", &B, &nb, &w, &p) != 4) return 3;
   std::vector<Sys> entries((size_t)B);
   for (Sys& s : entries) {
-    s.nb = nb; s.w = w; s.p = p; s.ldab = 3 * (int64_t)w + 1;
+    s = shaped(nb, w, p);
     s.band = read_doubles(f); s.U = read_doubles(f); s.C = read_doubles(f); s.rhs = read_doubles(f);
   }
   std::fclose(f);
@@ -216,7 +175,7 @@ static int dump(const char* path) {
 // ---------------------------------------------------------------- a planned system: n = 30 variables (one fixed), m = 20 rows
 // The unit assembles what the map says; the map here is a band of half-width 5 around a dominant diagonal and one border
 // column, each slot from one or two sources of [hvals | jvals | s1 | s2] -- no K of a model, which the unit does not need.
-struct Planned {
+struct PlannedMap {
   int32_t n = 30, m = 20;
   Csr A, T, Lo, S;
   std::vector<int32_t> order, map;
@@ -224,8 +183,8 @@ struct Planned {
   int w = 5, p = 1;
 };
 
-static Planned planned() {
-  Planned q;
+static PlannedMap planned() {
+  PlannedMap q;
   q.A = from_lengths(std::vector<int32_t>((size_t)q.m, 3), q.n);
   q.T = transposed(q.A);
   q.Lo.rows = q.Lo.cols = q.n;
@@ -281,7 +240,7 @@ int main(int argc, char** argv) {
 
   {  // good and failing entries in one batch: statuses 0, 1, 0, 3; the failed entries' solutions untouched, the others complete
     std::vector<Sys> entries;
-    for (int variant : {PLAIN, ZERO, TINY, PLANT}) entries.push_back(make(65, 7, 1, variant, 9));
+    for (Variant variant : {PLAIN, ZERO, TINY, PLANT}) entries.push_back(make(65, 7, 1, variant, 9));
     Batch b = pack(entries);
     OK(run(b));
     const double statuses[] = {0.0, 1.0, 0.0, 3.0};
@@ -360,7 +319,7 @@ int main(int argc, char** argv) {
   }
 
   // ---- the planned forms
-  const Planned q = planned();
+  const PlannedMap q = planned();
   const int32_t n = q.n, m = q.m;
   const int64_t N = n + m, nh = q.nh, nj = q.nj;
   set_problem(n, m, nj, nh);
