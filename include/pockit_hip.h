@@ -582,6 +582,37 @@ int pk_band_solve_multi_dev(pk_ctx* ctx, int32_t k, const double* d_rhs, int64_t
 int pk_solve_banded_multi(pk_ctx* ctx, int32_t k, const double* s1, const double* s2, const double* b /* k x (n + m) */,
                           double* x /* k x (n + m) */, double* rec /* 8 */);
 
+/* THE BAND SOLVE REFINED AGAINST THE TRUE K (kernels pk_bd_resid_k, pk_bd_refine_scalar_k, pk_bd_correct_k of the library;
+ * pk_band_refine.cpp).  A solution of pk_band_solve_dev is measured against K as the CSR values state it -- q = K x
+ * by pk_kkt_apply_dev's fixed-order application, r = b - q at the unknowns of the plan -- and corrected with the factors in place:
+ * d = K^-1 r by the launches of one solve, x = x + d.  The device decides when to stop.
+ * pk_band_refine_begin_dev is step 0: the product, the residual and the record.  The caller's six arrays must stay valid and
+ * unchanged (d_sol: by the caller) until the refinement ends; d_sol is refined in place.  pk_band_refine_advance_dev enqueues
+ * `steps` steps (solve, correction, product, residual, record).  Both enqueue on the context's stream and wait for nothing.
+ * pk_band_refine_record copies the record of 8 doubles and synchronises: 0 status (0 running, 1 converged, 2 stalled, 3 a value
+ * of r, x or b at an unknown is not finite, 4 the factorisation's own record is not 0: nothing is measured and d_sol is
+ * untouched); 1 corrections applied; 2 |r|inf; 3 |x|inf; 4 |b|inf; 5 rho = |r|inf / (min(|x|inf, 1e6 |b|inf) + |b|inf), 0.0
+ * when |r|inf is 0; 6 rho of step 0; 7 the rho before this one.  Behind step t: converged when t >= min_steps and rho <= tol;
+ * otherwise stalled when t >= 1 and rho > (1 - 1e-9) rho_prev (the correction that did not help stays in d_sol).  Once the
+ * status is not 0 further steps change neither d_sol nor the record: the result does not depend on how many steps were enqueued
+ * beyond the stop (each surplus step still costs its solve and its product).  A new plan or a new pk_band_factor_dev ends the
+ * refinement.  pk_solve_banded_refined is the host form on pk_linearize's values: uploads, factor, solve, begin, then one step
+ * at a time behind a read of the record until the status is not 0 or max_steps are done (status 5, exhausted, in the host copy
+ * rrec only); x comes down unless the band's status (rec) is not 0.
+ * Errors: 110 a null device pointer; 117 a CSR operator of J, J^T or H is not set; 119 a sharded context; 134 no plan or no
+ * factorisation, tol negative or not finite, min_steps or max_steps outside 0 ... 10, steps < 1; 135 advance or record without
+ * a begin; 136 no device memory (the message names the array); 60 a null host buffer; the host form also 118.  Nothing is
+ * enqueued or written after a refusal. */
+#define PK_BAND_REFINE_TOL 1.0e-10          /* the tolerance on rho the solver's loop passes */
+#define PK_BAND_REFINE_SINGULAR 1.0e-5      /* a final rho above this: the system counts as singular for this solve */
+#define PK_BAND_REFINE_MAX_STEPS 10         /* the most steps of one refinement */
+int pk_band_refine_begin_dev(pk_ctx* ctx, const double* d_hvals, const double* d_jvals, const double* d_s1, const double* d_s2,
+                             const double* d_rhs, double* d_sol, double tol, int32_t min_steps);
+int pk_band_refine_advance_dev(pk_ctx* ctx, int32_t steps);
+int pk_band_refine_record(pk_ctx* ctx, double* rec /* 8 */);
+int pk_solve_banded_refined(pk_ctx* ctx, const double* s1, const double* s2, const double* b, double* x, double* rec /* 8 */,
+                            double* rrec /* 8 */, double tol, int32_t min_steps, int32_t max_steps);
+
 #ifdef __cplusplus
 }
 #endif

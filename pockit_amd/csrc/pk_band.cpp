@@ -664,6 +664,7 @@ static void bd_scatter_host(const PkBandFamilyArgs& g, unsigned grid, unsigned y
 
 void free_band(pk_ctx* c) {
   PkBand& b = c->band;
+  release(b.d_refine); release(b.d_rpartial);
   release(b.d_map); release(b.d_order); release(b.d_where);
   release(b.d_work); release(b.d_ipiv); release(b.d_partial); release(b.d_scratch); release(b.d_raw);
   release(b.d_bwork); release(b.d_bipiv); release(b.d_bpartial); release(b.d_bscratch); release(b.d_braw);
@@ -889,6 +890,24 @@ int bd_host_form(pk_ctx* c, const char* who, size_t k, double*& scratch, size_t&
 
 }  // namespace
 
+// ---------------------------------------------------------------- for pk_band_refine.cpp (pk_runtime.h)
+int band_planned_ready(pk_ctx* c, bool factored, const char* who) {
+  if (const int rc = bd_plan_current(c, who)) return rc;
+  if (factored && !c->band.factored) return fail(c, 134, "%s: no factorisation (pk_band_plan, pk_band_factor_dev)", who);
+  return 0;
+}
+int band_planned_partial(pk_ctx* c, const char* who) {
+  PkBandArgs a = bd_planned(c).a;
+  return bd_partial(c, a, who);
+}
+int band_planned_solve(pk_ctx* c, const double* d_rhs, double* d_sol, const char* who) {
+  PkBandFamilyArgs g = bd_planned(c);
+  if (const int rc = bd_partial(c, g.a, who)) return rc;
+  g.a.rhs = d_rhs; g.a.sol = d_sol;
+  return bd_enqueue_solve(c, g, 1, c->stream);
+}
+const double* band_planned_record(pk_ctx* c) { return bd_planned(c).a.rec; }
+
 extern "C" {
 
 int pk_band_plan(pk_ctx* c, int64_t nb, int32_t w, int32_t p, const int32_t* order, const int32_t* map) {
@@ -932,7 +951,9 @@ int pk_band_plan(pk_ctx* c, int64_t nb, int32_t w, int32_t p, const int32_t* ord
   fresh.d_partial = c->band.d_partial; fresh.partial_cap = c->band.partial_cap;
   fresh.d_scratch = c->band.d_scratch; fresh.scratch_cap = c->band.scratch_cap;
   fresh.d_raw = c->band.d_raw; fresh.raw_cap = c->band.raw_cap;
-  c->band.d_partial = nullptr; c->band.d_scratch = nullptr; c->band.d_raw = nullptr;
+  fresh.d_refine = c->band.d_refine; fresh.refine_cap = c->band.refine_cap;      // (sized by n + m, not by the plan)
+  fresh.d_rpartial = c->band.d_rpartial; fresh.rpartial_cap = c->band.rpartial_cap;
+  c->band.d_partial = nullptr; c->band.d_scratch = nullptr; c->band.d_raw = nullptr; c->band.d_refine = nullptr; c->band.d_rpartial = nullptr;
   free_band(c);
   c->band = fresh;
   c->band.planned = true;
@@ -947,6 +968,7 @@ int pk_band_factor_dev(pk_ctx* c, const double* d_hvals, const double* d_jvals, 
   if ((rc = bd_context(c, who)) || (rc = bd_plan_current(c, who))) return rc;
   PkBandFamilyArgs g = bd_planned(c);
   g.a.hvals = d_hvals; g.a.jvals = d_jvals; g.a.s1 = d_s1; g.a.s2 = d_s2;
+  c->band.refining = false;      // (a refinement in progress measured the factors that go)
   if ((rc = bd_enqueue_factor(c, g, 1, true, c->stream))) return rc;
   c->band.factored = true;
   return 0;

@@ -25,6 +25,9 @@
 //                   band, bordered by the few dense unknowns (pk_bd_init_k, pk_bd_fill_k, pk_bd_panel_k, pk_bd_update_k,
 //                   pk_bd_prep_k, pk_bd_solve_k, pk_bd_dot_k, pk_bd_border_k, pk_bd_xb_k, pk_bd_scatter_k: the library's own kernels, one
 //                   family for a single system, a batch of entries and a block of right-hand sides)
+//   pk_band_refine.cpp  a solution of that solve measured against the true K (the CSR values) and refined with the factors in
+//                   place, the stop decided on the device (pk_bd_resid_k, pk_bd_refine_scalar_k, pk_bd_correct_k: the library's
+//                   own kernels)
 //   pk_solve.cpp    the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp: the context's growing
 //                   arrays (lib_reserve, also pk_merit.cpp's, pk_ipm.cpp's, pk_slack.cpp's and pk_band.cpp's), the common checks, the skeletons of record / advance / the host loop
 //   pk_error.cpp    fail(): where an error message is kept
@@ -263,6 +266,18 @@ struct PkBand {
   size_t mpartial_cap = 0;
   double* d_mscratch = nullptr;     // the host block form's [b (k rows) | s1 s2 | x (k rows)]
   size_t mscratch_cap = 0;
+  // the refinement (pk_band_refine.cpp: pk_band_refine_begin_dev ...): reserved by the first begin, kept across plans, released
+  // with the band's state
+  double* d_refine = nullptr;       // [r | d | q] of n + m doubles each, the 4 planes of partials, the record of 8
+  size_t refine_cap = 0;
+  double* d_rpartial = nullptr;     // pk_band_refine_step_dev's partials (its other arrays are the caller's)
+  size_t rpartial_cap = 0;
+  bool refining = false;            // between a begin and the next plan or factorisation
+  int32_t refine_t = 0;             // steps enqueued since the begin
+  const double *rf_hvals = nullptr, *rf_jvals = nullptr, *rf_s1 = nullptr, *rf_s2 = nullptr, *rf_rhs = nullptr;   // the caller's arrays
+  double* rf_sol = nullptr;
+  double rf_tol = 0.0;
+  int32_t rf_min_steps = 0;
 };
 
 // ---- mesh error estimation (pk_set_mesh_error_tables; pk_extras.cpp: free_mesh_error)
@@ -518,7 +533,14 @@ void free_ipm(pk_ctx* c);            // partial columns and scratch (with the pr
 void free_slack(pk_ctx* c);          // partial columns and scratch (with the problem)
 
 // ---- pk_band.cpp
-void free_band(pk_ctx* c);           // the plan and every array of the unit (with the problem)
+void free_band(pk_ctx* c);           // the plan and every array of the unit (with the problem), the refinement's too
+// what pk_band_refine.cpp asks of the planned system: is there a plan the CSR maps still fit (and a factorisation)?  (134); the
+// border's partial sums reserved ahead of a solve (136); K sol = rhs with the factors in place, in the launches of
+// pk_band_solve_dev on the context's stream; the device address of the factorisation's record
+int band_planned_ready(pk_ctx* c, bool factored, const char* who);
+int band_planned_partial(pk_ctx* c, const char* who);
+int band_planned_solve(pk_ctx* c, const double* d_rhs, double* d_sol, const char* who);
+const double* band_planned_record(pk_ctx* c);
 
 // ---- pk_solve.cpp: the host scaffolding of a device-resident solve, shared by pk_cg.cpp and pk_minres.cpp (no kernels)
 // An array of the context that grows when needed and never shrinks: the new one first, so the error (code: 127 for the merit

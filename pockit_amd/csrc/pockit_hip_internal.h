@@ -269,6 +269,15 @@ int pk_band_raw_batch_dev(pk_ctx* ctx, int32_t B, int64_t nb, int32_t w, int32_t
  * gives for it alone.  Errors 110, 134, 136. */
 int pk_band_raw_multi_dev(pk_ctx* ctx, int64_t nb, int32_t w, int32_t p, int32_t k, double* d_band, const double* d_U, const double* d_C,
                           const double* d_rhs, int64_t stride_rhs, int32_t* d_ipiv, double* d_x, int64_t stride_x, double* d_rec);
+/* ONE of the three kernels of the band solve's refinement (pk_band_refine.cpp) on an EXPLICIT length with caller-owned device arrays
+ * (the public forms call them with the context's work, len = n + m and the plan's classification).  step: 0 residual -- d_where
+ * or NULL (every element an unknown), d_b, d_q, d_x; writes r and the context's partials; 1 scalar -- reduces those partials,
+ * writes the record of 8 at d_rec for step number t (0: begin; d_band_rec or NULL: a band record whose status is asked first);
+ * 2 correct -- x = x + d at the unknowns while the record's status is 0.  Pointers a step does not use may be NULL.  Errors
+ * 110, 134 for step, len, t, tol or min_steps, 136. */
+int pk_band_refine_step_dev(pk_ctx* ctx, int step, int64_t len, const int32_t* d_where, const double* d_b, const double* d_q,
+                            double* d_x, const double* d_d, double* d_r, double* d_rec, const double* d_band_rec, double tol,
+                            int32_t min_steps, int32_t t);
 
 #ifdef __cplusplus
 }

@@ -359,6 +359,11 @@ def compile_batched(plan, src, output_share=1.0, extra_flags=()):
     return hipbuild.compile_model(batched_source(plan, src, output_share).source, fastmath=plan.system._fastmath, extra_flags=extra_flags)
 
 
+# The refinement of the band solve (PK_BAND_REFINE_* of include/pockit_hip.h): the tolerance on the residual ratio, the ratio
+# above which a system counts as singular for the solve that asked, the most steps of one refinement.
+BAND_REFINE_TOL, BAND_REFINE_SINGULAR, BAND_REFINE_MAX_STEPS = 1.0e-10, 1.0e-5, 10
+
+
 class Evaluator:
     #: the one build change with evidence behind it for the round-5 defect: SGPR spills to scratch memory
     SGPR_TO_SCRATCH = ("-mllvm", "-amdgpu-spill-sgpr-to-vgpr=0")
@@ -1430,6 +1435,30 @@ class Evaluator:
         self.ctx.check(self.ctx.lib.pk_band_record(self.ctx.handle, runtime.as_dp(rec)))
         return rec
 
+    def band_refine_begin_dev(self, d_hvals, d_jvals, d_s1, d_s2, d_rhs, d_sol, tol=BAND_REFINE_TOL, min_steps=0):
+        """Enqueue step 0 of the refinement of ``d_sol``, a solution of ``band_solve_dev`` for ``d_rhs`` with the factors of
+        ``band_factor_dev`` on the same four arrays: ``q = K sol`` by ``kkt_apply_dev``'s fixed-order application of the TRUE K
+        (the CSR values, not the assembled band), the residual at the plan's unknowns and the record.  The six arrays must stay
+        valid and unchanged until the refinement ends; ``d_sol`` is refined in place.  Not waited for."""
+        for op in ("J", "JT", "H"):
+            self._operator(op)
+        self.ctx.check(self.ctx.lib.pk_band_refine_begin_dev(self.ctx.handle, d_hvals, d_jvals, d_s1, d_s2, d_rhs, d_sol, float(tol),
+                                                             int(min_steps)))
+
+    def band_refine_advance_dev(self, steps=1):
+        """Enqueue ``steps`` steps of the refinement: ``d = K^-1 r`` with the factors in place (the launches of one solve), ``sol
+        += d`` while the record's status is 0, then the product, the residual and the record again.  The device decides: a step
+        behind a stop runs its solve and changes nothing else, so the result does not depend on how many steps were enqueued
+        beyond the stop.  Not waited for."""
+        self.ctx.check(self.ctx.lib.pk_band_refine_advance_dev(self.ctx.handle, int(steps)))
+
+    def band_refine_record(self):
+        """The refinement's record (8 doubles: status -- 0 running, 1 converged, 2 stalled, 3 non-finite, 4 the factorisation
+        failed --, corrections applied, ``|r|inf``, ``|x|inf``, ``|b|inf``, rho, rho of step 0, the rho before), waited for."""
+        rec = np.empty(8)
+        self.ctx.check(self.ctx.lib.pk_band_refine_record(self.ctx.handle, runtime.as_dp(rec)))
+        return rec
+
     def band_factor_batch_dev(self, B, d_hvals, d_jvals, d_s1, d_s2, strides=None):
         """Enqueue ``band_factor_dev`` for B systems (1 ... 16) behind the one plan in one launch sequence: entry e reads its
         arrays e strides behind the pointers.  ``strides``: the doubles between two entries of ``(hvals, jvals, s1, s2)``,
@@ -1656,15 +1685,28 @@ class BandInfo:
     """What a band factorisation and solve on the device reports (read-only): ``status`` by name, ``column`` (the failing
     column in permuted numbering, -1 without one), ``min_pivot`` and ``max_pivot`` (of the band part), ``width``, ``border``,
     ``interchanges`` (columns whose pivot moved a row), ``primal`` and ``dual`` (views of the solution's two blocks) and the raw
-    ``record`` of 8 doubles."""
+    ``record`` of 8 doubles.  After a refined solve (``solve_banded(refine=r)``, r > 0) also ``residual_ratio`` (rho of the
+    returned x), ``residual_ratio_start`` (rho of the unrefined solve), ``refinement_steps`` (corrections applied),
+    ``refinement`` ("converged", "stalled", "non_finite", "exhausted"; "failed" behind a failed factorisation) and the raw
+    ``refinement_record``; all None without one."""
     STATUS = {0: "solved", 1: "singular_band_pivot", 2: "singular_border", 3: "non_finite"}
-    __slots__ = ("_rec", "_x", "_n")
+    REFINEMENT = {1: "converged", 2: "stalled", 3: "non_finite", 4: "failed", 5: "exhausted"}
+    __slots__ = ("_rec", "_x", "_n", "_rrec")
 
-    def __init__(self, rec, x, n):
+    def __init__(self, rec, x, n, rrec=None):
         rec = np.array(rec, dtype=np.float64)
         rec.setflags(write=False)
-        for name, value in (("_rec", rec), ("_x", x), ("_n", int(n))):
+        if rrec is not None:
+            rrec = np.array(rrec, dtype=np.float64)
+            rrec.setflags(write=False)
+        for name, value in (("_rec", rec), ("_x", x), ("_n", int(n)), ("_rrec", rrec)):
             object.__setattr__(self, name, value)
+
+    refinement_record = property(lambda self: self._rrec)
+    refinement = property(lambda self: None if self._rrec is None else self.REFINEMENT[int(self._rrec[0])])
+    refinement_steps = property(lambda self: None if self._rrec is None else int(self._rrec[1]))
+    residual_ratio = property(lambda self: None if self._rrec is None else float(self._rrec[5]))
+    residual_ratio_start = property(lambda self: None if self._rrec is None else float(self._rrec[6]))
 
     def __setattr__(self, name, value):
         raise AttributeError("BandInfo is read-only")
@@ -2080,14 +2122,22 @@ class Linearization:
                                              int(check_every), runtime.as_dp(x), runtime.as_dp(rec)))
         return x, MinresInfo(rec, tol, x, self.n)
 
-    def solve_banded(self, b, s1=None, s2=None):
+    def solve_banded(self, b, s1=None, s2=None, refine=0):
         """Solve ``K x = b`` (``kkt_v``'s matrix with the Hessian) by the bordered band LU on the device (csrc/pk_band.cpp):
         the ordering is built from the CSR maps and the bounds' fixed variables (``pockit_amd.band.BandOrdering``; a
         ``ValueError`` where the band is too wide), one call uploads ``b``, ``s1``, ``s2`` and downloads ``x`` and the record.
         ``s1`` and ``s2``: a scalar, a vector or None (zeros).  Returns ``(x, info)``, ``info`` a ``BandInfo``; ``x`` is all
         NaN unless ``info.status == "solved"``.  Fixed variables (``v_lb == v_ub``) are out of the system: their ``x`` is 0.0.
-        Pivoting never leaves the band part: a K whose band part is singular reports ``"singular_band_pivot"``."""
+        Pivoting never leaves the band part: a K whose band part is singular reports ``"singular_band_pivot"``.
+
+        ``refine`` (0 ... 10): the most corrections of an iterative refinement against the true K (the CSR values), decided on the
+        device: the residual ratio ``rho = |b - K x|inf / (min(|x|inf, 1e6 |b|inf) + |b|inf)`` over the unknowns is measured, and
+        while it exceeds 1e-10 and keeps falling ``x += K^-1 (b - K x)`` with the factors in place.  ``info`` then has
+        ``residual_ratio``, ``residual_ratio_start``, ``refinement_steps`` and ``refinement``.  0 is the unrefined call."""
         from .band import BandOrdering
+
+        if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= refine <= BAND_REFINE_MAX_STEPS:
+            raise ValueError(f"refine must be an integer in 0 ... {BAND_REFINE_MAX_STEPS}")
 
         ev, _, s1, s2 = self._kkt_args(s1, s2, True)
         size = self.n + self.m
@@ -2101,6 +2151,11 @@ class Linearization:
         ev.band_plan(ordering)
         x, rec = np.full(size, np.nan), np.empty(8)
         dp = runtime.as_dp
+        if refine:
+            rrec = np.empty(8)
+            ev.ctx.check(ev.ctx.lib.pk_solve_banded_refined(ev.ctx.handle, dp(s1), dp(s2), dp(b), dp(x), dp(rec), dp(rrec), BAND_REFINE_TOL, 0,
+                                                            int(refine)))
+            return x, BandInfo(rec, x, self.n, rrec)
         ev.ctx.check(ev.ctx.lib.pk_solve_banded(ev.ctx.handle, dp(s1), dp(s2), dp(b), dp(x), dp(rec)))
         return x, BandInfo(rec, x, self.n)
 

@@ -48,7 +48,7 @@ def _stale(target, sources):
 # The files of the host runtime, stated once: build_runtime() compiles the sources and watches the headers, and
 # tests/test_runtime_sanitized.py builds its CPU-only binaries from the same lists.
 RUNTIME_SOURCES = [os.path.join(CSRC, name) for name in
-                   ("pk_runtime.cpp", "pk_shim.cpp", "pk_pool.cpp", "pk_shard.cpp", "pk_batch.cpp", "pk_extras.cpp", "pk_ops.cpp", "pk_reduce.cpp", "pk_merit.cpp", "pk_cg.cpp", "pk_minres.cpp", "pk_ipm.cpp", "pk_slack.cpp", "pk_band.cpp", "pk_solve.cpp", "pk_error.cpp")]
+                   ("pk_runtime.cpp", "pk_shim.cpp", "pk_pool.cpp", "pk_shard.cpp", "pk_batch.cpp", "pk_extras.cpp", "pk_ops.cpp", "pk_reduce.cpp", "pk_merit.cpp", "pk_cg.cpp", "pk_minres.cpp", "pk_ipm.cpp", "pk_slack.cpp", "pk_band.cpp", "pk_band_refine.cpp", "pk_solve.cpp", "pk_error.cpp")]
 # (the helper-thread pool and the error slot it reports into: no HIP in either)
 POOL_SOURCES = [os.path.join(CSRC, name) for name in ("pk_pool.cpp", "pk_error.cpp")]
 RUNTIME_HEADERS = [os.path.join(CSRC, name) for name in

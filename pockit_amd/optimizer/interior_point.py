@@ -72,6 +72,7 @@ import math
 
 import numpy as np
 
+from ..evaluator import BAND_REFINE_MAX_STEPS, BAND_REFINE_SINGULAR, BAND_REFINE_TOL
 from ._common import dictated_slots, postprocess, preprocess
 
 DEFAULTS = {"tol": 1e-8, "max_iter": 200, "mu_init": 0.1, "print_level": 0}
@@ -524,7 +525,7 @@ def _sensitivities(R, params, direct, status):
     return out
 
 
-def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band_attempts=1, sensitivity=None):
+def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band_attempts=1, sensitivity=None, band_refine=0):
     """Solve the NLP of ``system`` from ``guess`` (the shapes of ``ipopt.solve``); returns ``(solution, info)``.  ``info`` has
     cyipopt's keys ``x, g, obj_val, mult_g, mult_x_L, mult_x_U, status, status_msg`` and ``iterations``, ``mu``, ``error`` (the
     final E_0), ``linear_iterations`` (MINRES iterations in all; 0 on the direct and banded paths), ``regularisations``, and the slacks with
@@ -534,6 +535,11 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
     "banded" (module docstring: where the latter two work); with "banded" a ``ValueError`` of the ordering (band too wide, border
     too large) leaves the choice of "direct" to the caller.  ``band_attempts`` (1 ... 8, "banded" only): how many ``delta_w`` of the
     regularisation schedule are factored and solved together (module docstring); the iterates do not depend on it.
+    ``band_refine`` (0 ... 10, "banded" only, not with ``band_attempts > 1``): the most corrections of the iterative refinement every
+    band solve gets against the true K (``band_refine_begin_dev``: tolerance 1e-10 on the residual ratio, the device decides); an
+    attempt whose final ratio exceeds 1e-5, or whose refinement met a non-finite value, counts as a failed factorisation.  Then
+    ``info`` has ``refinement_steps`` (corrections in all) and ``residual_ratio`` (the largest ratio of an accepted step).  With 0 no
+    call is added and neither key appears.
 
     ``sensitivity`` (with "direct" or "banded"): None, ``"fixed"`` -- every variable that equal bounds hold, that is not a slot the
     transcription dictates and that has a non-empty column in J or H -- or a mapping ``{"variables": [NLP slots], "rows":
@@ -553,17 +559,24 @@ def solve(system, guess, optimizer_options=None, *, linear_solver="direct", band
     if band_attempts != 1 and linear_solver != "banded":
         raise ValueError('band_attempts other than 1 needs linear_solver="banded"')
     band_attempts = int(band_attempts)
+    if isinstance(band_refine, bool) or not isinstance(band_refine, (int, np.integer)) or not 0 <= band_refine <= BAND_REFINE_MAX_STEPS:
+        raise ValueError(f"band_refine must be an integer in 0 ... {BAND_REFINE_MAX_STEPS}")
+    if band_refine and linear_solver != "banded":
+        raise ValueError('band_refine other than 0 needs linear_solver="banded"')
+    if band_refine and band_attempts > 1:
+        raise ValueError("band_refine is not offered with band_attempts > 1: the batch form is not refined")
+    band_refine = int(band_refine)
     opt = options(optimizer_options)
     params = sensitivity_parameters(system, sensitivity, linear_solver)
     x0, bare, _ = preprocess(system, guess, None)
     R = _Resident(system, x0)
     try:
-        return _iterate(system, R, opt, bare, linear_solver, band_attempts, params)
+        return _iterate(system, R, opt, bare, linear_solver, band_attempts, params, band_refine)
     finally:
         R.ev.set_bounds()            # the plan's bounds again: a later merit_scan measures against them, not against the fixed slots
 
 
-def _iterate(system, R, opt, bare, linear_solver, band_attempts, params=None):
+def _iterate(system, R, opt, bare, linear_solver, band_attempts, params=None, band_refine=0):
     """The loop of ``solve`` on the resident iterate ``R``."""
     ev, at, torch, n, m = R.ev, R.at, R.torch, R.n, R.m
     tol, mu = opt["tol"], opt["mu_init"]
@@ -594,7 +607,8 @@ def _iterate(system, R, opt, bare, linear_solver, band_attempts, params=None):
             return curvature, delta, step_sq
         return None
 
-    iterations = linear_iterations = 0
+    iterations = linear_iterations = refinement_steps = 0
+    residual_ratio = 0.0
     status, e_0 = -1, math.inf
     while True:
         q = R.measure(mu)
@@ -658,9 +672,20 @@ def _iterate(system, R, opt, bare, linear_solver, band_attempts, params=None):
                 R.to_kernels()
                 ev.band_factor_dev(at(R.ch), at(R.cj), at(R.s1), at(R.s2))
                 ev.band_solve_dev(at(R.rhs), at(R.sol))
+                if band_refine:
+                    ev.band_refine_begin_dev(at(R.ch), at(R.cj), at(R.s1), at(R.s2), at(R.rhs), at(R.sol), BAND_REFINE_TOL, 0)
                 br = ev.band_record()
                 if br[0] != 0.0 or not np.all(np.isfinite(br)):
                     continue
+                if band_refine:
+                    rr = ev.band_refine_record()
+                    while rr[0] == 0.0 and rr[1] < band_refine:
+                        ev.band_refine_advance_dev(1)
+                        rr = ev.band_refine_record()
+                    refinement_steps += int(rr[1])
+                    if rr[0] in (3.0, 4.0) or not rr[5] <= BAND_REFINE_SINGULAR:
+                        continue
+                    attempt_ratio = float(rr[5])
             else:
                 k_s1 = R.s1 + R.fixed_s1
                 R.to_kernels()
@@ -692,6 +717,8 @@ def _iterate(system, R, opt, bare, linear_solver, band_attempts, params=None):
                 R.to_kernels()
             step = passes(delta)
             if step is not None:
+                if band_refine:
+                    residual_ratio = max(residual_ratio, attempt_ratio)
                 break
         if step is None:
             status = -2
@@ -770,5 +797,7 @@ def _iterate(system, R, opt, bare, linear_solver, band_attempts, params=None):
                      mult_s_L=R.down(R.yl, m).copy(), mult_s_U=R.down(R.yu, m).copy())
     if sens is not None:
         info["sensitivity"] = sens
+    if band_refine:
+        info["refinement_steps"], info["residual_ratio"] = refinement_steps, residual_ratio
     ev._invalidate_x()
     return postprocess(system, x, bare), info

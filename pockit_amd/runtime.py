@@ -161,6 +161,10 @@ PROTOTYPES = {
     "pk_solve_banded_batch": (C.c_int, [vp, C.c_int32, dp, dp, dp, dp, dp]),
     "pk_band_solve_multi_dev": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64]),
     "pk_solve_banded_multi": (C.c_int, [vp, C.c_int32, dp, dp, dp, dp, dp]),
+    "pk_band_refine_begin_dev": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int32]),
+    "pk_band_refine_advance_dev": (C.c_int, [vp, C.c_int32]),
+    "pk_band_refine_record": (C.c_int, [vp, dp]),
+    "pk_solve_banded_refined": (C.c_int, [vp, dp, dp, dp, dp, dp, dp, C.c_double, C.c_int32, C.c_int32]),
     # ---- host shim (csrc/pockit_hip_internal.h)
     "pk_eval_hessc_prepared": (C.c_int, [vp, dp, C.c_double, dp, C.c_int]),
     "pk_same_x": (C.c_int, [vp, dp]),
@@ -235,6 +239,7 @@ PROTOTYPES = {
     "pk_band_raw_batch_dev": (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
                                         vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64]),
     "pk_band_raw_multi_dev": (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp]),
+    "pk_band_refine_step_dev": (C.c_int, [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int32, C.c_int32]),
 }
 EXPORTS = list(PROTOTYPES)
 

@@ -151,6 +151,78 @@ def banded_rows(args, models, ipm):
     return lines
 
 
+def refine_rows(args, models, ipm):
+    """``--banded --refine R``: whole solves with ``band_refine`` = R alternating with 0, what the refinement
+    saw over a solve (the largest and the median rho_0, the corrections), and one begin and one step at the start point (enqueue
+    and wait, host-landed)."""
+    from pockit_amd.band import BandOrdering
+
+    r = args.refine
+    lines = [f"ip_solve_probe --banded --refine {r}: interior_point.solve, linear_solver \"banded\", band_refine {r} alternating with 0 (tol 1e-8); "
+             f"median [min, max] of {args.runs} runs each, host-landed"]
+    for name, scheme, mesh, num_point in MODELS:
+        ns = importlib.import_module(f"pockit_amd.{scheme}")
+        system, _, guess = getattr(models, name)(ns, mesh, num_point)
+        ev = system.evaluator
+        seen = []
+        record = ev.band_refine_record
+
+        def spy():
+            rec = record()
+            seen.append(rec.copy())
+            return rec
+
+        times, infos = {0: [], r: []}, {}
+        ipm.solve(system, guess, linear_solver="banded", band_refine=r)                    # warm-up
+        ev.band_refine_record = spy
+        for _ in range(args.runs):
+            for k in (0, r):
+                del seen[:]
+                t0 = time.perf_counter()
+                _, infos[k] = ipm.solve(system, guess, linear_solver="banded", band_refine=k)
+                times[k].append(time.perf_counter() - t0)
+        del ev.band_refine_record
+        lines.append(f"{name}({scheme}, {mesh}, {num_point}): n {system.plan.n}, m {system.plan.m}")
+        for k in (0, r):
+            info = infos[k]
+            per = [t / max(1, info["iterations"]) for t in times[k]]
+            lines.append(f"    band_refine {k}: {spread(times[k], 1e3)} ms per solve, {spread(per, 1e3, '9.2f')} ms per iteration; status {info['status']}, "
+                         f"{info['iterations']} Newton iterations, {info['regularisations']} regularised, f = {info['obj_val']:.10f}, E_0 {info['error']:.2e}")
+        first = np.array([rec[6] for rec in seen if rec[0] != 4.0])
+        if len(first):
+            lines.append(f"    rho_0 over the last solve ({len(first)} records read): largest {first.max():.2e}, median {np.median(first):.2e}; "
+                         f"{infos[r]['refinement_steps']} corrections, the largest accepted rho {infos[r]['residual_ratio']:.2e}")
+        R = ipm._Resident(system, ipm.preprocess(system, guess, None)[0])
+        R.evaluate()
+        R.to_torch()
+        R.ev.band_plan(BandOrdering(R.map_j, R.map_h, R.free))
+        R.s1 = R.up(np.ones(R.n))
+        R.s2 = R.up(np.where(R.ineq, 1.0, 0.0))
+        R.rhs = R.up(np.random.default_rng(3).standard_normal(R.n + R.m))
+        R.to_kernels()
+        at = R.at
+        ev.band_factor_dev(at(R.ch), at(R.cj), at(R.s1), at(R.s2))
+        t_b, t_s = [], []
+        for _ in range(args.runs + 1):
+            ev.band_solve_dev(at(R.rhs), at(R.sol))
+            ev.sync()
+            t0 = time.perf_counter()
+            ev.band_refine_begin_dev(at(R.ch), at(R.cj), at(R.s1), at(R.s2), at(R.rhs), at(R.sol), 0.0, 0)
+            ev.sync()
+            t1 = time.perf_counter()
+            ev.band_refine_advance_dev(1)
+            ev.sync()
+            t2 = time.perf_counter()
+            t_b.append(t1 - t0)
+            t_s.append(t2 - t1)
+        rec = ev.band_refine_record()
+        lines.append(f"    begin   {spread(t_b[1:], 1e3, '9.3f')} ms (the product with K, the residual, the record)")
+        lines.append(f"    step    {spread(t_s[1:], 1e3, '9.3f')} ms (one solve, the correction, the product, the residual, the record); at the start point "
+                     f"rho_0 {rec[6]:.2e}, rho_1 {rec[5]:.2e}, status {int(rec[0])}")
+        ev.close()
+    return lines
+
+
 def banded_batch_rows(args, models, ipm):
     """one batched factorisation and one batched solve at B = 1, 2, 4, 8 against B single ones in a row on
     the same values (enqueue and wait, host-landed, alternating), then whole solves with ``band_attempts`` = 1, 2, 4."""
@@ -294,6 +366,7 @@ def main():
     ap.add_argument("--multi", action="store_true", help="the rows of the block solve and the sensitivities instead (DESIGN.md section 27)")
     ap.add_argument("--banded-batch", action="store_true", help="the rows of the batched band LU instead (DESIGN.md section 24)")
     ap.add_argument("--banded", action="store_true", help="the rows of the banded step solver instead (DESIGN.md section 23)")
+    ap.add_argument("--refine", type=int, default=0, help="with --banded: band_refine R alternating with 0 instead (DESIGN.md section 29)")
     ap.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -301,12 +374,16 @@ def main():
     ap.add_argument("--trust-constr-large", type=int, default=1, help="trust-constr runs on the large model (each takes minutes)")
     ap.add_argument("--large-maxiter", type=int, default=400, help="trust-constr's maxiter on the large model")
     args = ap.parse_args()
+    if args.refine and not args.banded:
+        ap.error("--refine needs --banded")
+    if not 0 <= args.refine <= 10:
+        ap.error("--refine takes 0 ... 10")
     import models
     from pockit_amd.optimizer import interior_point as ipm
     from pockit_amd.optimizer import scipy as scipy_solver
 
     if args.banded or args.banded_batch or args.multi:
-        text = "\n".join((multi_rows if args.multi else banded_batch_rows if args.banded_batch else banded_rows)(args, models, ipm)) + "\n"
+        text = "\n".join((multi_rows if args.multi else banded_batch_rows if args.banded_batch else refine_rows if args.refine else banded_rows)(args, models, ipm)) + "\n"
         print(text, end="")
         if args.out:
             with open(args.out, "a" if args.append else "w") as fh:
